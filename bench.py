@@ -10,10 +10,13 @@ Infinity Cache) so the stream comes from HBM.
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 What the one JSON line says (rank 0 prints it):
-  value / ms_per_step   steps timed between barrier + device sync on both sides, max over ranks.  K = 20 steps of a 16 us
-                        kernel last 0.3 ms, of which opening and closing the region is ~15 %, so a timed region is `repeats`
-                        back-to-back passes of K steps (no sync inside; `timed_steps` = K x repeats >= 20 ms) and the median
-                        of five regions is reported: the per-step number does not depend on K.
+  value / ms_per_step   after W untimed warm-up steps, exactly K steps timed back to back in ONE region between barrier +
+                        device sync on both sides (no sync inside), max over ranks; ms_per_step = region / K.  Opening and
+                        closing the region costs ~50 us, so pick K for a region of >= 20 ms (K = 2000 by default; ms_per_step
+                        tells how many steps that takes).
+  --dump-outputs DIR    after the timed steps, what the timed path's LAST step computed (skinned position / normal / tangent,
+                        float32, one .npy each; a fixed seeded vertex sample past 64 MB) goes to DIR.  The inputs are seeded:
+                        the same arguments give the same inputs, so two builds can be compared output for output.
   roofline.frac         follows from ONE kernel: algorithmic bytes / the kernel's own duration (launches serialized on
                         one stream, HIP events: what rocprofv3 --kernel-trace reports per dispatch).
   roofline.overlapped   the same bytes / the time per launch of the timed region, where independent launches overlap on
@@ -50,7 +53,8 @@ N_VERTS = 1_000_000
 N_BONES = 256
 BYTES_PER_VERTEX = 100          # 60 read + 40 written
 HBM_PEAK_GBPS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
-MIN_REGION_MS = 20.0            # a timed region shorter than this is repeated (see module docstring)
+DUMP_BUDGET_BYTES = 64_000_000  # --dump-outputs: at most this much in all; larger outputs are dumped as a seeded vertex sample
+DUMP_SAMPLE_SEED = 1234
 CHECK_THREADS = 8               # OpenMP threads of the oracle in the parity legs.  NOT all cores: on hosts with a CPU quota a burst of
                                 # 128 threads right before a host-bound timed loop gets the process throttled, and the loop measures that
 EXCHANGE_TIMEOUT_S = 120        # N > 1: the RCCL exchange leg may take this long before the line is printed without it
@@ -368,7 +372,8 @@ def parse():
     ap.add_argument("--no-check", action="store_true", help="skip the parity spot-check before timing")
     ap.add_argument("--no-extras", action="store_true", help="skip the C2 / C3 / C5 sub-records")
     ap.add_argument("--extras-only", action="store_true", help="(internal) run only the sub-records, in this fresh process, and print them")
-    ap.add_argument("--max-repeats", type=int, default=4000)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy (float32)")
     ap.add_argument("--no-pmc", action="store_true", help="do not measure roofline.traffic now (two rocprofv3 --pmc passes of ~15 s in child processes); replay the builder's")
     ap.add_argument("--one-process", action="store_true",
                     help="N > 1 without a launcher and without torch.distributed: ONE process drives all N GPUs, one fyx context and one "
@@ -422,6 +427,27 @@ def dl(ctx, t, first: int, count: int) -> np.ndarray:
 def zero(ctx, t) -> None:
     z = np.zeros(t.numel(), np.float32)
     ctx._check(ctx._l.fyx_memcpy_h2d(ctx._h, ctypes.c_void_p(t.data_ptr()), z.ctypes.data_as(ctypes.c_void_p), z.nbytes))
+
+
+def dump_outputs(out_dir: str, segments) -> dict:
+    """--dump-outputs: the skinned position / normal / tangent streams a caller of the timed path receives, as out_dir/pos.npy (n, 3),
+    normal.npy (n, 3) and tangent.npy (n, 4), float32.  `segments` = [(ctx, (pos, normal, tangent) device buffers, first vertex, vertex
+    count)], concatenated in order (a mesh cut over several GPUs).  Past DUMP_BUDGET_BYTES a fixed seeded sample of vertices is written,
+    their indices in vertex_index.npy (float64)."""
+    streams = (("pos", 3), ("normal", 3), ("tangent", 4))
+    host = {name: np.concatenate([dl(c, bufs[k], first * w, count * w).reshape(count, w) for c, bufs, first, count in segments])
+            for k, (name, w) in enumerate(streams)}
+    n = len(host["pos"])
+    idx = None
+    if n * 4 * sum(w for _, w in streams) > DUMP_BUDGET_BYTES:
+        k = (DUMP_BUDGET_BYTES - 4096) // (4 * sum(w for _, w in streams) + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, k, replace=False))
+        host = {name: a[idx] for name, a in host.items()}
+        host["vertex_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "files": sorted(name + ".npy" for name in host), "n_verts": n, "sampled": idx is not None}
 
 
 def lbs_parity(ctx, mesh, pal, d_out, n_chk: int) -> dict:
@@ -1263,6 +1289,7 @@ def main_one_process(args, reason: str) -> None:
     sets = max(2, min(args.sets, 4))
     fn = ctxs[0]._l.fyx_lbs_skin_device
     weak_calls, strong_calls, strong_bufs, strong_bufs_padded, strong_calls_padded = [], [], [], [], []
+    weak_outs0 = []       # GPU 0's output sets of the weak leg
     shard_p = sharding.vertex_range_padded(nv, 0, n)[2]
     for g, c in enumerate(ctxs):
         d_pal = c.to_device(pal)
@@ -1272,8 +1299,8 @@ def main_one_process(args, reason: str) -> None:
             o = tuple(c.malloc_streams([nv * 12 + 64, nv * 12 + 64, nv * 16 + 64]))
             calls.append(partial(fn, c._h, ctypes.c_uint64(100 + s_), ctypes.c_void_p(d_pal.ptr), ctypes.c_uint32(nb), ctypes.c_uint32(1),
                                  ctypes.c_void_p(o[0].ptr), ctypes.c_void_p(o[1].ptr), ctypes.c_void_p(o[2].ptr)))
-            if g == 0 and s_ == 0:
-                first_out = o
+            if g == 0:
+                weak_outs0.append(o)
         weak_calls.append(calls)
         # strong: this GPU's shard of the ONE mesh, written in place into full-size buffers (ragged cut) / padded buffers (equal cut)
         b, e = sharding.vertex_range_native(nv, g, n)
@@ -1294,7 +1321,7 @@ def main_one_process(args, reason: str) -> None:
     if not args.no_check:
         weak_calls[0][0]()
         ctxs[0].sync()
-        parity = lbs_parity(ctxs[0], mesh, pal, tuple(_Ptr(b.ptr) for b in first_out), 20_000)
+        parity = lbs_parity(ctxs[0], mesh, pal, tuple(_Ptr(b.ptr) for b in weak_outs0[0]), 20_000)
         if not parity["bit_exact"]:
             raise SystemExit("one-process bench: GPU 0's output differs from the oracle")
 
@@ -1331,6 +1358,17 @@ def main_one_process(args, reason: str) -> None:
     s_c = timed(lambda g, i: chk(strong_calls[g]()), args.steps, args.warmup)
     weak_v, weak_ms, strong_v, strong_ms = float(nv) * n * args.steps / w, w * 1e3 / args.steps, float(nv) * args.steps / s_c, s_c * 1e3 / args.steps
     as_weak = args.scaling == "weak"
+    dumped = None
+    if args.dump_outputs:       # the timed steps index from 0: the last one wrote set (steps - 1) % sets (weak), every GPU's shard (strong)
+        if as_weak:
+            dumped = dump_outputs(args.dump_outputs, [(ctxs[0], tuple(_Ptr(b.ptr) for b in weak_outs0[(args.steps - 1) % sets]), 0, nv)])
+        else:
+            segs = []
+            for g, c in enumerate(ctxs):
+                b, e = sharding.vertex_range_native(nv, g, n)
+                if e > b:
+                    segs.append((c, tuple(_Ptr(x.ptr) for x in strong_bufs[g]), b, e - b))
+            dumped = dump_outputs(args.dump_outputs, segs)
     out = {"metric": "skinned vertices/sec at 1M verts/256 bones; achieved HBM GB/s vs peak",
            "value": weak_v if as_weak else strong_v, "unit": "vertices/s", "n_gpus": n, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": weak_ms if as_weak else strong_ms, "higher_is_better": True, "scaling": "weak" if as_weak else "strong",
@@ -1342,7 +1380,7 @@ def main_one_process(args, reason: str) -> None:
                                    "weak_value = every GPU its own 1 M-vertex mesh"),
                       "process_group": f"none: ONE process drives the {n} GPUs (fyx_comm_init_all / fyx_allgather_skinned_all), one host thread per GPU; {reason}",
                       "devices": devices, "sharding": "contiguous vertex range per GPU, palette replicated", "n_ranks": n, "sets": sets},
-           "roofline": None, "parity": parity,
+           "roofline": None, "parity": parity, "dump_outputs": dumped,
            "strong_value": strong_v, "strong_ms_per_step": strong_ms, "weak_value": weak_v, "weak_ms_per_step": weak_ms,
            "value_with_gather": None, "value_with_gather_form": None, "comm_error": None,
            "timing_note": "host clock between fyx_sync of every context before and after the launches (no torch, no events across devices)",
@@ -1533,10 +1571,9 @@ def main():
         return float(t[0])
 
     def timed_regions(step, steps, warmup, first_index=0):
-        """One timed region = `repeats` back-to-back passes of `steps` launches between barrier + device sync (no sync
-        inside); `repeats` is 1 when `steps` launches already last MIN_REGION_MS, otherwise what makes the region that
-        long (from an untimed pilot pass), so that the fixed cost of opening and closing a region (~50 us) does not
-        decide a number quoted per step.  Returns (repeats, per-region wall seconds (max over ranks), GPU ms)."""
+        """`warmup` untimed steps, then ONE timed region of exactly `steps` back-to-back launches between barrier + device
+        sync (no sync inside): the last timed step is step(first_index + warmup + steps - 1).  Returns (repeats = 1,
+        [region wall seconds (max over ranks)], [GPU ms])."""
         for i in range(warmup):
             step(first_index + i)
         n = first_index + warmup
@@ -1553,14 +1590,8 @@ def main():
             n += count
             return max_over_ranks(time.perf_counter() - t0), max_over_ranks(g)
 
-        pilot, _ = region(steps)
-        repeats = max(1, min(args.max_repeats, int(np.ceil(MIN_REGION_MS * 1e-3 / max(pilot, 1e-6)))))
-        walls, gpus = [], []
-        for _ in range(5 if repeats > 1 else 1):
-            w, g = region(steps * repeats)
-            walls.append(w)
-            gpus.append(g)
-        return repeats, walls, gpus
+        w, g = region(steps)
+        return 1, [w], [g]
 
 
     seed = synth.SEED_BASE + 4
@@ -1599,9 +1630,13 @@ def main():
 
     strong = None
     weak_regions = None
+    dumped = None
     if run_weak:
         weak_regions = timed_regions(step, args.steps, args.warmup)
         repeats, walls, gpus = weak_regions
+        if args.dump_outputs and args.scaling == "weak" and rank == 0:
+            ctx.sync()
+            dumped = dump_outputs(args.dump_outputs, [(ctx, outs[(args.warmup + args.steps - 1) % n_sets], 0, nv)])
     # ---- the kernel alone: launches serialized on ONE stream (HIP-event average per launch == rocprofv3 kernel duration) --
     n_ser = max(500, min(args.steps, 2000))
     ctx.set_option("lbs.streams", 1)
@@ -1850,6 +1885,9 @@ def main():
             if not head["bit_exact"]:
                 raise SystemExit("strong scaling: rank 0's shard differs from the oracle")
         r_c, w_c, g_c = timed_regions(lambda i: sstep(i, False), args.steps, args.warmup)
+        if args.dump_outputs and args.scaling == "strong" and not (args.allgather and have_comm) and rank == 0:
+            ctx.sync()        # compute only: what rank 0's last step wrote is its own shard of the mesh
+            dumped = dump_outputs(args.dump_outputs, [(ctx, alls[(args.warmup + args.steps - 1) % sets2], b, e - b)])
         sizes = [sharding.vertex_range_native(full.n_verts, r, world) for r in range(world)]
         strong = {"workload": f"C4 as written: {full.n_verts} verts / {args.bones} bones cut by contiguous vertex range over {world} GPU(s), "
                               "palette replicated; every rank writes its shard in place into the full buffers",
@@ -1865,6 +1903,7 @@ def main():
             """Every rank ends up holding the WHOLE skinned mesh (checked on rank 0 against the oracle, head and tail), then the
             timed regions with the exchange in them.  `form`: option comm.form (0 one broadcast per shard, 1 grouped send / recv,
             2 one in-place all-gather per stream over the padded cut).  Returns (record, regions) on rank 0's behalf; all ranks take part."""
+            nonlocal dumped
             ctx.set_option("comm.form", form)
             padded = form == 2
             bufs = alls2[0] if padded else alls[0]
@@ -1881,6 +1920,9 @@ def main():
                 got = dl(ctx, bufs[0], (full.n_verts - n_chk) * 3, n_chk * 3).reshape(-1, 3)      # (vertex v lies at position v in either cut)
                 ok = bool(lbs_parity(ctx, full, pal, bufs, n_chk)["bit_exact"] and np.array_equal(got, ref["pos"]))
             r_g, w_g, g_g = timed_regions(lambda i: sstep(i, True, padded), args.steps, args.warmup)
+            if args.dump_outputs and args.scaling == "strong" and args.allgather and form == 0 and rank == 0:
+                ctx.sync()        # --allgather times this form as `value`: every rank receives the whole gathered mesh
+                dumped = dump_outputs(args.dump_outputs, [(ctx, alls[(args.warmup + args.steps - 1) % sets2], 0, full.n_verts)])
             rec = {"value": full.n_verts * args.steps * r_g / float(np.median(w_g)), "unit": "vertices/s",
                    "ms_per_step": float(np.median(w_g)) * 1e3 / (args.steps * r_g), "timed_steps": args.steps * r_g,
                    "collective": "fyx_allgather_skinned: one grouped RCCL op per frame (40 B/vertex), " +
@@ -1922,8 +1964,9 @@ def main():
             "ms_per_step": region * 1e3 / timed_steps, "higher_is_better": True, "scaling": args.scaling,
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "timed_steps": timed_steps, "repeats": repeats, "timed_regions": len(walls), "region_ms": [w * 1e3 for w in walls],
-            "timing_note": f"a timed region = {repeats} back-to-back passes of --steps {args.steps} launches between barrier + sync "
-                           f"(no sync inside), so that it lasts >= {MIN_REGION_MS:.0f} ms; median of {len(walls)} regions",
+            "dump_outputs": dumped,
+            "timing_note": f"ONE timed region of exactly --steps {args.steps} back-to-back launches between barrier + sync (no sync inside), "
+                           f"after --warmup {args.warmup} untimed ones; opening and closing it costs ~50 us, so regions shorter than ~20 ms overstate ms_per_step",
             "config": {"workload": f"C4: {nv} verts / {args.bones} bones per GPU, 4-influence LBS of position+normal+tangent, "
                                    f"{args.sets} rotating 100 MB buffer sets, "
                                    f"{'random' if args.random_bones else 'spatially coherent'} bone indices"
@@ -2072,6 +2115,7 @@ def main():
                         out["value"] = float(args.verts) * args.steps * r_g / float(np.median(w_g))
                         out["ms_per_step"] = float(np.median(w_g)) * 1e3 / (args.steps * r_g)
                         out["timed_steps"], out["repeats"], out["region_ms"] = args.steps * r_g, r_g, [w * 1e3 for w in w_g]
+                        out["dump_outputs"] = dumped
                 else:
                     st[key] = {"value": None, "note": f"the exchange failed: {err}"}
             if err is not None and world > 1:

@@ -84,3 +84,28 @@ def test_the_headline_line_is_short_and_its_full_record_carries_the_box_facts(tm
         assert line["roofline"]["traffic_source"] == "pmc_in_this_run" and line["roofline"]["traffic"] == pytest.approx(tm["hbm_bytes_per_launch"], rel=1e-5)
     else:
         assert d["roofline"]["traffic"] is None or "not measured in this run" in d["roofline"]["traffic_source"]
+
+
+@pytest.mark.gpu
+def test_steps_are_exact_and_the_dump_is_the_last_timed_step(tmp_path):
+    """--steps K times exactly K launches (no hidden repetition of the region), and --dump-outputs writes what the last of them computed:
+    the 1 M-vertex C4 mesh skinned, bit for bit the oracle's on the same seeded inputs."""
+    import numpy as np
+    import oracle
+    from fyrox_amd import synth
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    out = tmp_path / "outputs"
+    line, full = _run(["--steps", "7", "--warmup", "3", "--sets", "3", "--no-extras", "--no-cpu-baseline", "--no-pmc", "--dump-outputs", str(out)], env, tmp_path)
+    assert line["steps"] == 7 and line["timed_steps"] == 7 and line["repeats"] == 1 and full["timed_regions"] == 1
+    assert full["ms_per_step"] == pytest.approx(full["region_ms"][0] / 7, rel=1e-9)
+    assert line["ms_per_step"] == pytest.approx(full["ms_per_step"], rel=1e-5)      # the line keeps 6 significant digits
+    assert full["dump_outputs"]["n_verts"] == 1_000_000 and not full["dump_outputs"]["sampled"]
+    seed = synth.SEED_BASE + 4
+    mesh = synth.make_mesh(1_000_000, 256, seed)
+    ref = oracle.lbs_skin(mesh.pos, mesh.weights, mesh.indices, synth.make_palette(256, seed), mesh.normal, mesh.tangent, threads=8)
+    total = 0
+    for name in ("pos", "normal", "tangent"):
+        got = np.load(out / f"{name}.npy")
+        total += got.nbytes
+        assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), ref[name].view(np.uint32)), name
+    assert total <= 64_000_000

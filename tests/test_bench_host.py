@@ -1,8 +1,11 @@
 """The parts of bench.py that need no GPU (the driver runs bench.py on an MI355X; these keep its host-only pieces
 from rotting between GPU runs)."""
+import ctypes
 import importlib.util
 import os
 import sys
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -170,3 +173,66 @@ def test_the_line_of_several_gpus_carries_both_scalings():
     assert d["exchange_legs"]["with_allgather_sendrecv"] == {"value": 3.1e9, "ms_per_step": 0.32} and d["exchange_legs"]["with_allgather_padded"]["value"] is None
     assert "compute_only" not in d["exchange_legs"] and d["gathered_equals_oracle"] is True and d["crowd_value"] == 7.7e11
     assert "kernel_options" not in d["config"] and d["config"]["n_ranks"] == 8
+
+
+class _HostBuffer:
+    """Stands in for a device buffer: dump_outputs reads it through the context's fyx_memcpy_d2h."""
+    def __init__(self, a):
+        self.a = np.ascontiguousarray(a, np.float32).ravel()
+
+    def data_ptr(self):
+        return self.a.ctypes.data
+
+
+class _HostCtx:
+    """The two members of a fyx context that bench.dl uses, with the device-to-host copy done by memmove."""
+    _h = None
+
+    class _l:
+        @staticmethod
+        def fyx_memcpy_d2h(h, dst, src, nbytes):
+            ctypes.memmove(dst, src, nbytes)
+            return 0
+
+    @staticmethod
+    def _check(rc):
+        assert rc == 0
+
+
+def test_dump_outputs_writes_each_stream_in_float32_and_samples_past_the_budget(tmp_path):
+    """--dump-outputs: pos / normal / tangent of the caller's vertices, float32, shards concatenated in order; a mesh too large for the
+    budget is dumped as the same seeded vertex sample on every run, with the sample's vertex indices beside it."""
+    b = _bench()
+    rng = np.random.default_rng(7)
+    n = 1000
+    streams = [rng.standard_normal((n, w)).astype(np.float32) for w in (3, 3, 4)]
+    bufs = tuple(_HostBuffer(a) for a in streams)
+    rec = b.dump_outputs(str(tmp_path / "whole"), [(_HostCtx, bufs, 0, 600), (_HostCtx, bufs, 600, 400)])
+    assert rec["files"] == ["normal.npy", "pos.npy", "tangent.npy"] and rec["n_verts"] == n and not rec["sampled"]
+    for name, a in zip(("pos", "normal", "tangent"), streams):
+        got = np.load(tmp_path / "whole" / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, a)
+    orig = b.DUMP_BUDGET_BYTES
+    try:
+        b.DUMP_BUDGET_BYTES = 4096 + 48 * 100          # room for 100 of the 1000 vertices
+        recs = [b.dump_outputs(str(tmp_path / f"sample{k}"), [(_HostCtx, bufs, 0, n)]) for k in range(2)]
+    finally:
+        b.DUMP_BUDGET_BYTES = orig
+    assert all(r["sampled"] and "vertex_index.npy" in r["files"] for r in recs)
+    idx = np.load(tmp_path / "sample0" / "vertex_index.npy")
+    assert idx.dtype == np.float64 and len(idx) == 100 and np.array_equal(idx, np.load(tmp_path / "sample1" / "vertex_index.npy"))
+    total = sum(os.path.getsize(tmp_path / "sample0" / f) for f in recs[0]["files"])
+    assert total <= 4096 + 48 * 100 + 4 * 128        # npy headers aside, within the budget
+    for name, a in zip(("pos", "normal", "tangent"), streams):
+        got = np.load(tmp_path / "sample0" / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, a[idx.astype(np.int64)])
+
+
+def test_the_dump_option_parses():
+    b = _bench()
+    argv, sys.argv = sys.argv, ["bench.py", "--steps", "7", "--warmup", "3", "--dump-outputs", "out"]
+    try:
+        a = b.parse()
+    finally:
+        sys.argv = argv
+    assert (a.steps, a.warmup, a.dump_outputs) == (7, 3, "out")

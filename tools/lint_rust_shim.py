@@ -11,15 +11,16 @@ that sank the first version of the shim: names that do not exist in the referenc
   * every extern function called (`fyx_*`) must be declared in bindings/rust/fyrox_hip_sys.rs (generated from the header)
     and be called with as many arguments as it is declared with.
 
-It is a grep-level check, not a type checker: it cannot see a wrong receiver type or a borrow error.  It reads
-/root/reference, so it only runs where the reference is (the build container), and the CPU test that calls it skips
-elsewhere.   python tools/lint_rust_shim.py  ->  exit code 0 / 1, findings on stdout."""
+It is a grep-level check, not a type checker: it cannot see a wrong receiver type or a borrow error.  It reads a checkout
+of the Fyrox sources named by the environment variable FYROX_SRC (the workspace root), so it only runs where one is, and the
+CPU test that calls it skips elsewhere.   FYROX_SRC=/path/to/Fyrox python tools/lint_rust_shim.py  ->  exit code 0 / 1,
+findings on stdout."""
 import os
 import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+REF = os.environ.get("FYROX_SRC", "")
 SHIM = [os.path.join(ROOT, "bindings", "rust", f) for f in ("fyrox_hip.rs", "fyrox_hip_flatten.rs")]
 SYS = os.path.join(ROOT, "bindings", "rust", "fyrox_hip_sys.rs")
 CRATES = ["fyrox-impl/src", "fyrox-animation/src", "fyrox-core/src", "fyrox-math/src", "fyrox-resource/src", "fyrox-graph/src"]
