@@ -1449,18 +1449,13 @@ __device__ __forceinline__ void local_matrix(const float* __restrict__ st, float
     out[15] = 1.0f;
 }
 
-// nalgebra Matrix4 * Matrix4: per result column an axpy chain over k (a_col_k * b_kj + y).
+// nalgebra Matrix4 * Matrix4 (column-major), element by element (mat4_elem).
 __device__ __forceinline__ void mat4_mul(const float* a, const float* b, float* out) {
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float y = a[i] * b[j * 4];
-            y = a[4 + i] * b[j * 4 + 1] + y;
-            y = a[8 + i] * b[j * 4 + 2] + y;
-            y = a[12 + i] * b[j * 4 + 3] + y;
-            out[j * 4 + i] = y;
-        }
+        for (int i = 0; i < 4; ++i)
+            out[j * 4 + i] = mat4_elem(f32x4{a[i], a[4 + i], a[8 + i], a[12 + i]}, f32x4{b[j * 4], b[j * 4 + 1], b[j * 4 + 2], b[j * 4 + 3]});
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1741,7 +1736,7 @@ __device__ __forceinline__ bool pose_update_body(const PoseFrameDev& f, const Ri
     // level-synchronous global = parent.global * local; a root multiplies by the identity, as
     // the reference does for a node without a valid parent.  What each thread does in the walk was fetched at the top.
     if constexpr (WIDE) {
-        // Lane (g, i, j) forms element (row i, column j) of the matrix of group g's node: mat4_mul's chain for that element.  No
+        // Lane (g, i, j) forms element (row i, column j) of the matrix of group g's node (mat4_elem).  No
         // lane asks whether it has a node (padding entries multiply the identity by zeros into a slot nobody reads) or whether its
         // node has a parent (a root's parent slot holds the identity): a chunk is straight-line code, and the barrier closes a level.
         // Measured (tools/exp/r04_stamps.py, nine levels): 1.3 us against 2.1 us with per-level offsets and a lane test, 2.2 - 3.1 us
@@ -1755,12 +1750,7 @@ __device__ __forceinline__ bool pose_update_body(const PoseFrameDev& f, const Ri
             const uint32_t node = ent & 2047u, slot = (ent >> 11) & 2047u;
             const f4 b = reinterpret_cast<const f4*>(l_local + (size_t)node * 16)[j];
             const float* a = l_global + (size_t)slot * 16 + i;
-            const float a0 = a[0], a1 = a[4], a2 = a[8], a3 = a[12];
-            float y = a0 * b.x;
-            y = a1 * b.y + y;
-            y = a2 * b.z + y;
-            y = a3 * b.w + y;
-            l_global[(size_t)node * 16 + e] = y;          // e = j * 4 + i
+            l_global[(size_t)node * 16 + e] = mat4_elem(f4{a[0], a[4], a[8], a[12]}, b);          // e = j * 4 + i
             if (__builtin_amdgcn_readfirstlane((int)ent) & (1 << 22)) sync();     // (the flag is the same in all sixteen entries of a chunk)
             ent = nent;
         }
@@ -1812,27 +1802,10 @@ __device__ __forceinline__ bool pose_update_body(const PoseFrameDev& f, const Ri
         for (int k = 0; k < 4; ++k) {
             const uint32_t e = threadIdx.x + (uint32_t)k * 256u;
             if (e >= skin->n_bones * 4u) continue;
-            const uint32_t b = e >> 2, c = e & 3u;
-            f4 y;
-            if (q_node[k] < 0) {
-                y = f4{c == 0 ? 1.0f : 0.0f, c == 1 ? 1.0f : 0.0f, c == 2 ? 1.0f : 0.0f, c == 3 ? 1.0f : 0.0f};
-            } else {
-                const f4 b4 = q_bb[k];
-                const f4* a = reinterpret_cast<const f4*>(l_global) + (size_t)q_node[k] * 4;
-                const f4 a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3];
-                y.x = a0.x * b4.x; y.x = a1.x * b4.y + y.x; y.x = a2.x * b4.z + y.x; y.x = a3.x * b4.w + y.x;
-                y.y = a0.y * b4.x; y.y = a1.y * b4.y + y.y; y.y = a2.y * b4.z + y.y; y.y = a3.y * b4.w + y.y;
-                y.z = a0.z * b4.x; y.z = a1.z * b4.y + y.z; y.z = a2.z * b4.z + y.z; y.z = a3.z * b4.w + y.z;
-                y.w = a0.w * b4.x; y.w = a1.w * b4.y + y.w; y.w = a2.w * b4.z + y.w; y.w = a3.w * b4.w + y.w;
-            }
-            float* r = reinterpret_cast<float*>(rows + b * 3u);
-            *reinterpret_cast<f32x2*>(r + 2u * c) = f32x2{y.x, y.y};
-            r[8u + c] = y.z;
-            reinterpret_cast<float*>(row3 + b)[c] = y.w;
-            pj |= y.w != (c == 3u ? 1.0f : 0.0f);
+            const uint32_t c = e & 3u;
+            pj |= commit_column(rows, row3, e >> 2, c, bone_palette_column(reinterpret_cast<const f4*>(l_global), q_bb[k], q_node[k], c));
         }
-        const bool wave_pj = __any(pj) != 0;
-        if ((threadIdx.x & 63u) == 0) wave_flag[threadIdx.x >> 6] = wave_pj ? 1u : 0u;
+        publish_projective(pj, wave_flag, threadIdx.x & 63u, threadIdx.x >> 6);      // (read by frame_skin_body behind this barrier)
         __syncthreads();
         FSTAMP(6);
         return true;
@@ -1876,20 +1849,7 @@ __device__ __forceinline__ bool pose_update_body(const PoseFrameDev& f, const Ri
             for (int k = 0; k < 4; ++k) {
                 const uint32_t e = e0 + (uint32_t)k * bdim;
                 if (e >= n_cols) continue;
-                const uint32_t j = e & 3u;
-                f4 y;
-                if (node[k] < 0) {
-                    y = f4{j == 0 ? 1.0f : 0.0f, j == 1 ? 1.0f : 0.0f, j == 2 ? 1.0f : 0.0f, j == 3 ? 1.0f : 0.0f};
-                } else {
-                    const f4 b4 = bb[k];
-                    const f4* a = reinterpret_cast<const f4*>(l_global) + (size_t)node[k] * 4;
-                    const f4 a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3];
-                    y.x = a0.x * b4.x; y.x = a1.x * b4.y + y.x; y.x = a2.x * b4.z + y.x; y.x = a3.x * b4.w + y.x;
-                    y.y = a0.y * b4.x; y.y = a1.y * b4.y + y.y; y.y = a2.y * b4.z + y.y; y.y = a3.y * b4.w + y.y;
-                    y.z = a0.z * b4.x; y.z = a1.z * b4.y + y.z; y.z = a2.z * b4.z + y.z; y.z = a3.z * b4.w + y.z;
-                    y.w = a0.w * b4.x; y.w = a1.w * b4.y + y.w; y.w = a2.w * b4.z + y.w; y.w = a3.w * b4.w + y.w;
-                }
-                out[e] = y;
+                out[e] = bone_palette_column(reinterpret_cast<const f4*>(l_global), bb[k], node[k], e & 3u);
             }
         }
     }
@@ -1983,7 +1943,7 @@ __device__ __forceinline__ void frame_skin_body(const PoseFrameDev& fr, const Ri
     const f32x4* rows = reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(lds) + wide_update_lds(rig.n_nodes, rig.n_chunks) + 16u);
     const f32x4* row3 = rows + 3u * j.n_bones;
     const uint32_t* wave_flag = reinterpret_cast<const uint32_t*>(row3 + j.n_bones);
-    const bool projective = (wave_flag[0] | wave_flag[1] | wave_flag[2] | wave_flag[3]) != 0;
+    const bool projective = read_projective<4>(wave_flag);
     auto process = [&](VertexIn<7>& c_, uint32_t v_c) {
         pin_vertex(c_);
         const Skinned o = skin_vertex<EXACT, 7>(rows, row3, projective, c_.id, c_.w, c_.p.x, c_.p.y, c_.p.z,
@@ -2179,12 +2139,9 @@ __global__ __launch_bounds__(256) void palette_gather_kernel(const float* __rest
         if (node < 0) {
             y = (i == j) ? 1.0f : 0.0f;
         } else {
-            const float* a = global + ((size_t)inst * n_nodes + node) * 16;
-            const float* bb = inv_bind + (size_t)node * 16;
-            y = a[i] * bb[j * 4];
-            y = a[4 + i] * bb[j * 4 + 1] + y;
-            y = a[8 + i] * bb[j * 4 + 2] + y;
-            y = a[12 + i] * bb[j * 4 + 3] + y;
+            const float* a = global + ((size_t)inst * n_nodes + node) * 16 + i;
+            const float* bb = inv_bind + (size_t)node * 16 + j * 4;
+            y = mat4_elem(f32x4{a[0], a[4], a[8], a[12]}, f32x4{bb[0], bb[1], bb[2], bb[3]});
         }
         out[e] = y;
     }

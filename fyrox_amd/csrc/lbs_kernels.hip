@@ -61,21 +61,69 @@ namespace fyx {
 
 constexpr int kSkinBlock = 512;   // threads per workgroup of lbs_skin / lbs_skin_batch / the crowd kernel's vertex tile
 
+// One segment (= the units [seg_b, seg_e) of one instance of one mesh): shared by lbs_skin (segments = the instances of a) and
+// lbs_skin_batch (segments = the batch's table).  palette: this instance's matrices; out_base: its first vertex in the outputs;
+// first: no wave of the workgroup has used the LDS palette yet.  cur / nxt: the wave's two vertex register sets, owned by the
+// kernel so that they live across segments: declared in here, they gave some instantiations more VGPRs than the kernels had
+// before this body was shared -- lbs_skin<false, 2> 80 -> 82, one resident workgroup per CU fewer and 14 % slower.
 template <bool EXACT, int MASK>
-__global__ __launch_bounds__(kSkinBlock) void lbs_skin(LbsArgs a, uint32_t units_per_inst, uint32_t total_units) {
+__device__ __forceinline__ void skin_segment(const LbsArgs& a, const float* __restrict__ palette, size_t out_base, uint32_t seg_b,
+                                             uint32_t seg_e, bool first, unsigned char* smem, VertexIn<MASK>& cur,
+                                             VertexIn<MASK>& nxt) {
     constexpr bool NT = true;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr uint32_t WPB = kSkinBlock / 64;
     f32x4* rows = reinterpret_cast<f32x4*>(smem);
     f32x4* row3 = rows + 3 * a.n_bones;
     uint32_t* wave_flag = reinterpret_cast<uint32_t*>(row3 + a.n_bones);
-
-    constexpr uint32_t WPB = kSkinBlock / 64;
     const int tid = threadIdx.x;
     const uint32_t lane = tid & 63, wave = tid >> 6;
+
+    // Order of issue matters: vector-memory loads retire in order (vmcnt), so the palette
+    // fetch goes FIRST and the first unit's vertex loads right behind it.  The LDS commit
+    // below then waits for the (L2-resident, fast) palette only, while the vertex loads --
+    // a cold HBM access at kernel start -- stay in flight across the staging barrier.
+    const PaletteRegs pr = palette_fetch(palette, a.n_bones, tid);
+    // this wave's vertices of the segment: whole units dealt round-robin to the waves (unit k of the segment -> wave k % WPB)
+    const uint32_t ve = seg_e * 64 < a.n_verts ? seg_e * 64 : a.n_verts;
+    constexpr uint32_t vstep = WPB * 64;
+    uint32_t base = (seg_b + wave) * 64;
+    uint32_t v = base + lane;
+    cur = load_vertex<NT, MASK>(a, v < ve ? v : 0);
+
+    if (!first) __syncthreads();  // every wave is done with the previous palette
+    const bool projective = block_projective<WPB>(palette_commit(pr, a.n_bones, rows, row3, tid), wave_flag, lane, wave);
+    // Opaque use point: nothing that consumes the first unit's vertex data may be scheduled
+    // above the staging barrier (it would drag the wait for those loads up with it).
+    pin_vertex(cur);
+
+    while (base < ve) {  // wave-uniform
+        const uint32_t bn = base + vstep;
+        const uint32_t vn = bn + lane;
+        if (bn < ve) nxt = load_vertex<NT, MASK>(a, vn < ve ? vn : 0);
+        const Skinned o = skin_vertex<EXACT, MASK>(rows, row3, projective, cur.id, cur.w, cur.p.x,
+                                                   cur.p.y, cur.p.z, cur.n.x, cur.n.y, cur.n.z,
+                                                   cur.t.x, cur.t.y, cur.t.z);
+        if (v < ve) {
+            const size_t ov = out_base + v;
+            if constexpr (MASK & 1) st3<NT>(a.out_pos + ov * 3, o.px, o.py, o.pz);
+            if constexpr (MASK & 2) st3<NT>(a.out_nrm + ov * 3, o.nx, o.ny, o.nz);
+            if constexpr (MASK & 4)
+                stg<NT>(reinterpret_cast<f32x4*>(a.out_tan) + ov, f32x4{o.tx, o.ty, o.tz, cur.t.w});
+        }
+        cur = nxt;
+        base = bn;
+        v = vn;
+    }
+}
+
+template <bool EXACT, int MASK>
+__global__ __launch_bounds__(kSkinBlock) void lbs_skin(LbsArgs a, uint32_t units_per_inst, uint32_t total_units) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const uint32_t u_begin = (uint32_t)(((uint64_t)blockIdx.x * total_units) / gridDim.x);
     const uint32_t u_end = (uint32_t)(((uint64_t)(blockIdx.x + 1) * total_units) / gridDim.x);
     if (u_begin >= u_end) return;
 
+    VertexIn<MASK> cur, nxt;
     const uint32_t inst_first = u_begin / units_per_inst;
     const uint32_t inst_last = (u_end - 1) / units_per_inst;
 
@@ -83,51 +131,8 @@ __global__ __launch_bounds__(kSkinBlock) void lbs_skin(LbsArgs a, uint32_t units
         const uint32_t inst_u0 = inst * units_per_inst;
         const uint32_t seg_b = (u_begin > inst_u0 ? u_begin : inst_u0) - inst_u0;
         const uint32_t seg_e = (u_end < inst_u0 + units_per_inst ? u_end : inst_u0 + units_per_inst) - inst_u0;
-
-        // Order of issue matters: vector-memory loads retire in order (vmcnt), so the palette
-        // fetch goes FIRST and the first unit's vertex loads right behind it.  The LDS commit
-        // below then waits for the (L2-resident, fast) palette only, while the vertex loads --
-        // a cold HBM access at kernel start -- stay in flight across the staging barrier.
-        const PaletteRegs pr = palette_fetch(a.palette + (size_t)inst * a.n_bones * 16, a.n_bones, tid);
-        // this wave's vertices of the segment: whole units dealt round-robin to the waves (unit k of the segment -> wave k % WPB)
-        const uint32_t ve = seg_e * 64 < a.n_verts ? seg_e * 64 : a.n_verts;
-        constexpr uint32_t vstep = WPB * 64;
-        uint32_t base = (seg_b + wave) * 64;
-        uint32_t v = base + lane;
-        VertexIn<MASK> cur = load_vertex<NT, MASK>(a, v < ve ? v : 0);
-
-        if (inst != inst_first) __syncthreads();  // every wave is done with the previous palette
-        const bool pj = palette_commit(pr, a.n_bones, rows, row3, tid);
-        // block-wide OR with the single barrier the staging needs anyway: one flag per wave
-        const bool wave_pj = __any(pj) != 0;
-        if (lane == 0) wave_flag[wave] = wave_pj ? 1u : 0u;
-        __syncthreads();
-        bool projective = false;
-#pragma unroll
-        for (uint32_t wv = 0; wv < WPB; ++wv) projective |= wave_flag[wv] != 0;
-        // Opaque use point: nothing that consumes the first unit's vertex data may be scheduled
-        // above the staging barrier (it would drag the wait for those loads up with it).
-        pin_vertex(cur);
-
-        while (base < ve) {  // wave-uniform
-            const uint32_t bn = base + vstep;
-            const uint32_t vn = bn + lane;
-            VertexIn<MASK> nxt;
-            if (bn < ve) nxt = load_vertex<NT, MASK>(a, vn < ve ? vn : 0);
-            const Skinned o = skin_vertex<EXACT, MASK>(rows, row3, projective, cur.id, cur.w, cur.p.x,
-                                                       cur.p.y, cur.p.z, cur.n.x, cur.n.y, cur.n.z,
-                                                       cur.t.x, cur.t.y, cur.t.z);
-            if (v < ve) {
-                const size_t ov = (size_t)inst * a.n_verts + v;
-                if constexpr (MASK & 1) st3<NT>(a.out_pos + ov * 3, o.px, o.py, o.pz);
-                if constexpr (MASK & 2) st3<NT>(a.out_nrm + ov * 3, o.nx, o.ny, o.nz);
-                if constexpr (MASK & 4)
-                    stg<NT>(reinterpret_cast<f32x4*>(a.out_tan) + ov, f32x4{o.tx, o.ty, o.tz, cur.t.w});
-            }
-            cur = nxt;
-            base = bn;
-            v = vn;
-        }
+        skin_segment<EXACT, MASK>(a, a.palette + (size_t)inst * a.n_bones * 16, (size_t)inst * a.n_verts, seg_b, seg_e,
+                                  inst == inst_first, smem, cur, nxt);
     }
 }
 
@@ -172,27 +177,15 @@ __global__ __launch_bounds__(kDynBlock) void lbs_skin_dyn(LbsArgs a, uint32_t to
     uint32_t* ticket = wave_flag + 16;
 
     constexpr uint32_t WPB = kDynBlock / 64;
-    constexpr int PIECES = 1024 / kDynBlock;     // 16-byte palette columns per thread (n_bones <= 256)
     const int tid = threadIdx.x;
     const uint32_t lane = tid & 63, wave = tid >> 6;
     const uint32_t u_begin = (uint32_t)(((uint64_t)blockIdx.x * total_units) / gridDim.x);
     const uint32_t n_units = (uint32_t)(((uint64_t)(blockIdx.x + 1) * total_units) / gridDim.x) - u_begin;
 
-    // Palette columns first: column c of bone b is piece 4 b + c, and a wave fetches 64 consecutive pieces (16 bones, one dense
-    // 1 KB request).  WHICH lane takes which piece of those 64 is chosen for the LDS commit below: the 16 lanes one ds_write_b64
-    // serves together take the four columns of bones {0, 2, 4, 6} (or {1, 3, 5, 7}) of an octet, whose 8-dword (x, y) windows at
-    // the 48-byte row stride start at dwords 0 / 24 / 48 / 72 = banks 0 / 24 / 16 / 8: the four windows tile all 32 banks.  (With
-    // lanes in piece order the group was bones {0, 1, 2, 3}: windows at banks 0 / 12 / 24 / 4, the fourth on top of the first --
-    // SQ_LDS_BANK_CONFLICT 65 536 cycles per launch in round 2.)
-    const uint32_t n_pieces = a.n_bones * 4;
-    const uint32_t grp16 = lane >> 4, in16 = lane & 15;
-    const uint32_t my_piece = ((uint32_t)tid & ~63u) + 4 * (8 * (grp16 >> 1) + 2 * (in16 >> 2) + (grp16 & 1)) + (in16 & 3);
-    f32x4 col[PIECES];
-#pragma unroll
-    for (int i = 0; i < PIECES; ++i) {
-        const uint32_t piece = my_piece + (uint32_t)i * kDynBlock;
-        col[i] = reinterpret_cast<const f32x4*>(a.palette)[piece < n_pieces ? piece : n_pieces - 1];
-    }
+    // palette columns first (see PaletteColumns)
+    PaletteColumns<kDynBlock> pal;
+    const uint32_t piece0 = pal.first_piece(tid);
+    pal.fetch(a.palette, a.n_bones, piece0);
     // the wave's first two units (tickets wave and WPB + wave; the launcher guarantees n_units >= 2 WPB)
     const VtxBuffers vb = make_vtx_buffers(a);
     auto vertex_of = [&](uint32_t t) -> uint32_t { return (u_begin + t) * 64 + lane; };
@@ -201,28 +194,7 @@ __global__ __launch_bounds__(kDynBlock) void lbs_skin_dyn(LbsArgs a, uint32_t to
     VertexIn<MASK> B;   // requested behind the staging barrier (see above)
 
     if (tid == 0) *ticket = 2 * WPB;
-    bool pj = false;
-    // Packed-math layout (see stage_palette): A = (m00, m10, m01, m11)  B = (m02, m12, t0, t1)  C = (m20, m21, m22, t2)
-    // row3 = (m30, m31, m32, m33); a thread holds column c = (m0c, m1c, m2c, m3c) of bone b: (x, y) is one 8-byte store, z and
-    // w one 4-byte store each (the 32 lanes of a 4-byte store cover a whole octet of bones: dwords 12 b + 8 + c, all banks).
-#pragma unroll
-    for (int i = 0; i < PIECES; ++i) {
-        const uint32_t piece = my_piece + (uint32_t)i * kDynBlock;
-        if (piece < n_pieces) {
-            const uint32_t b = piece >> 2, c = piece & 3;
-            float* r = reinterpret_cast<float*>(rows + b * 3);
-            *reinterpret_cast<f32x2*>(r + 2 * c) = f32x2{col[i].x, col[i].y};
-            r[8 + c] = col[i].z;
-            reinterpret_cast<float*>(row3 + b)[c] = col[i].w;
-            pj |= col[i].w != (c == 3 ? 1.0f : 0.0f);
-        }
-    }
-    const bool wave_pj = __any(pj) != 0;
-    if (lane == 0) wave_flag[wave] = wave_pj ? 1u : 0u;
-    __syncthreads();
-    bool projective = false;
-#pragma unroll
-    for (uint32_t wv = 0; wv < WPB; ++wv) projective |= wave_flag[wv] != 0;
+    const bool projective = block_projective<WPB>(pal.commit(a.n_bones, piece0, rows, row3), wave_flag, lane, wave);
     pin_vertex(A);
     B = load_vertex_buf<MASK, kDynLoadAux>(vb, vB);
 
@@ -234,9 +206,7 @@ __global__ __launch_bounds__(kDynBlock) void lbs_skin_dyn(LbsArgs a, uint32_t to
     };
     // draw the next unit into a register set whose math is done; false when the workgroup's range is used up
     auto refill = [&](VertexIn<MASK>& n_, uint32_t& v_n) -> bool {
-        uint32_t t = 0;
-        if (lane == 0) t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        t = __builtin_amdgcn_readfirstlane(t);
+        const uint32_t t = draw_ticket(ticket, lane);
         if (t >= n_units) return false;
         v_n = vertex_of(t);
         n_ = load_vertex_buf<MASK, kDynLoadAux>(vb, v_n);
@@ -468,73 +438,36 @@ hipError_t launch_lbs(const LbsArgs& a, const LbsTuning& t, hipStream_t stream) 
 // ---------------------------------------------------------------------------------------
 #define FYX_CONSTANT __attribute__((address_space(4)))
 
+// One table entry as the arguments of one instance.
+__device__ __forceinline__ LbsArgs seg_args(const FYX_CONSTANT LbsSegDev* sg) {
+    LbsArgs a;
+    a.pos = sg->pos; a.nrm = sg->nrm; a.tan = sg->tan; a.wgt = sg->wgt; a.idx = sg->idx;
+    a.palette = sg->palette;
+    a.out_pos = sg->out_pos; a.out_nrm = sg->out_nrm; a.out_tan = sg->out_tan;
+    a.n_verts = sg->n_verts; a.n_bones = sg->n_bones; a.n_instances = 1;
+    return a;
+}
+
 template <bool EXACT, int MASK>
-__global__ __launch_bounds__(512) void lbs_skin_batch(const LbsSegDev* __restrict__ segs_g, uint32_t n_segs,
-                                                     const uint32_t* __restrict__ block_seg, uint32_t total_units) {
-    constexpr uint32_t WPB = 8;
-    constexpr bool NT = true;
+__global__ __launch_bounds__(kSkinBlock) void lbs_skin_batch(const LbsSegDev* __restrict__ segs_g, uint32_t n_segs,
+                                                            const uint32_t* __restrict__ block_seg, uint32_t total_units) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const FYX_CONSTANT LbsSegDev* segs = (const FYX_CONSTANT LbsSegDev*)segs_g;
-    const int tid = threadIdx.x;
-    const uint32_t lane = tid & 63, wave = tid >> 6;
     const uint32_t u_begin = (uint32_t)(((uint64_t)blockIdx.x * total_units) / gridDim.x);
     const uint32_t u_end = (uint32_t)(((uint64_t)(blockIdx.x + 1) * total_units) / gridDim.x);
     if (u_begin >= u_end) return;
     bool first = true;
+    VertexIn<MASK> cur, nxt;
     for (uint32_t seg = block_seg[blockIdx.x]; seg < n_segs; ++seg) {   // workgroup-uniform
         const uint32_t s_u0 = segs[seg].unit0;
         if (s_u0 >= u_end) break;
-        LbsArgs a;
-        a.pos = segs[seg].pos; a.nrm = segs[seg].nrm; a.tan = segs[seg].tan; a.wgt = segs[seg].wgt; a.idx = segs[seg].idx;
-        a.palette = segs[seg].palette;
-        a.out_pos = segs[seg].out_pos; a.out_nrm = segs[seg].out_nrm; a.out_tan = segs[seg].out_tan;
-        a.n_verts = segs[seg].n_verts; a.n_bones = segs[seg].n_bones; a.n_instances = 1;
+        const LbsArgs a = seg_args(segs + seg);
         const uint32_t upi = (a.n_verts + 63) / 64;
         if (s_u0 + upi <= u_begin) continue;
         const uint32_t seg_b = (u_begin > s_u0 ? u_begin : s_u0) - s_u0;
         const uint32_t seg_e = (u_end < s_u0 + upi ? u_end : s_u0 + upi) - s_u0;
-
-        f32x4* rows = reinterpret_cast<f32x4*>(smem);
-        f32x4* row3 = rows + 3 * a.n_bones;
-        uint32_t* wave_flag = reinterpret_cast<uint32_t*>(row3 + a.n_bones);
-        // palette fetch first, the first unit's vertex loads right behind it (see lbs_skin)
-        const PaletteRegs pr = palette_fetch(a.palette, a.n_bones, tid);
-        const uint32_t vb = (seg_b + wave) * 64;
-        const uint32_t ve = seg_e * 64 < a.n_verts ? seg_e * 64 : a.n_verts;
-        constexpr uint32_t vstep = WPB * 64;
-        uint32_t base = vb;
-        uint32_t v = base + lane;
-        VertexIn<MASK> cur = load_vertex<NT, MASK>(a, v < ve ? v : 0);
-
-        if (!first) __syncthreads();  // every wave is done with the previous palette
+        skin_segment<EXACT, MASK>(a, a.palette, 0, seg_b, seg_e, first, smem, cur, nxt);
         first = false;
-        const bool pj = palette_commit(pr, a.n_bones, rows, row3, tid);
-        const bool wave_pj = __any(pj) != 0;
-        if (lane == 0) wave_flag[wave] = wave_pj ? 1u : 0u;
-        __syncthreads();
-        bool projective = false;
-#pragma unroll
-        for (uint32_t wv = 0; wv < WPB; ++wv) projective |= wave_flag[wv] != 0;
-        pin_vertex(cur);
-
-        while (base < ve) {  // wave-uniform
-            const uint32_t bn = base + vstep;
-            const uint32_t vn = bn + lane;
-            VertexIn<MASK> nxt;
-            if (bn < ve) nxt = load_vertex<NT, MASK>(a, vn < ve ? vn : 0);
-            const Skinned o = skin_vertex<EXACT, MASK>(rows, row3, projective, cur.id, cur.w, cur.p.x,
-                                                       cur.p.y, cur.p.z, cur.n.x, cur.n.y, cur.n.z,
-                                                       cur.t.x, cur.t.y, cur.t.z);
-            if (v < ve) {
-                if constexpr (MASK & 1) st3<NT>(a.out_pos + (size_t)v * 3, o.px, o.py, o.pz);
-                if constexpr (MASK & 2) st3<NT>(a.out_nrm + (size_t)v * 3, o.nx, o.ny, o.nz);
-                if constexpr (MASK & 4)
-                    stg<NT>(reinterpret_cast<f32x4*>(a.out_tan) + v, f32x4{o.tx, o.ty, o.tz, cur.t.w});
-            }
-            cur = nxt;
-            base = bn;
-            v = vn;
-        }
     }
 }
 
@@ -551,7 +484,6 @@ template <bool EXACT, int MASK>
 __global__ __launch_bounds__(kBatchDynBlock) void lbs_skin_batch_dyn(const LbsSegDev* __restrict__ segs_g, uint32_t n_segs,
                                                                      const uint32_t* __restrict__ block_seg, uint32_t total_units) {
     constexpr uint32_t WPB = kBatchDynBlock / 64;
-    constexpr int PIECES = 1024 / kBatchDynBlock;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint32_t* const wave_flag = reinterpret_cast<uint32_t*>(smem);          // 4 words; word 8: the ticket; the palette from byte 64
     uint32_t* const ticket = wave_flag + 8;
@@ -562,30 +494,20 @@ __global__ __launch_bounds__(kBatchDynBlock) void lbs_skin_batch_dyn(const LbsSe
     const uint32_t u_begin = (uint32_t)(((uint64_t)blockIdx.x * total_units) / gridDim.x);
     const uint32_t u_end = (uint32_t)(((uint64_t)(blockIdx.x + 1) * total_units) / gridDim.x);
     if (u_begin >= u_end) return;
-    const uint32_t grp16 = lane >> 4, in16 = lane & 15;
-    const uint32_t my_piece = ((uint32_t)tid & ~63u) + 4 * (8 * (grp16 >> 1) + 2 * (in16 >> 2) + (grp16 & 1)) + (in16 & 3);   // (see lbs_skin_dyn)
+    const uint32_t piece0 = PaletteColumns<kBatchDynBlock>::first_piece(tid);
     bool first = true;
     for (uint32_t seg = block_seg[blockIdx.x]; seg < n_segs; ++seg) {   // workgroup-uniform
         const uint32_t s_u0 = segs[seg].unit0;
         if (s_u0 >= u_end) break;
-        LbsArgs a;
-        a.pos = segs[seg].pos; a.nrm = segs[seg].nrm; a.tan = segs[seg].tan; a.wgt = segs[seg].wgt; a.idx = segs[seg].idx;
-        a.palette = segs[seg].palette;
-        a.out_pos = segs[seg].out_pos; a.out_nrm = segs[seg].out_nrm; a.out_tan = segs[seg].out_tan;
-        a.n_verts = segs[seg].n_verts; a.n_bones = segs[seg].n_bones; a.n_instances = 1;
+        const LbsArgs a = seg_args(segs + seg);
         const uint32_t upi = (a.n_verts + 63) / 64;
         if (s_u0 + upi <= u_begin) continue;
         const uint32_t seg_b = (u_begin > s_u0 ? u_begin : s_u0) - s_u0;
         const uint32_t n_units = (u_end < s_u0 + upi ? u_end : s_u0 + upi) - s_u0 - seg_b;
         f32x4* const row3 = rows + 3 * a.n_bones;
 
-        const uint32_t n_pieces = a.n_bones * 4;
-        f32x4 col[PIECES];
-#pragma unroll
-        for (int i = 0; i < PIECES; ++i) {
-            const uint32_t piece = my_piece + (uint32_t)i * kBatchDynBlock;
-            col[i] = n_pieces ? reinterpret_cast<const f32x4*>(a.palette)[piece < n_pieces ? piece : n_pieces - 1] : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
+        PaletteColumns<kBatchDynBlock, true> pal;      // (a segment's mesh may have no bones)
+        pal.fetch(a.palette, a.n_bones, piece0);
         const VtxBuffers vb = make_vtx_buffers(a);
         auto vertex_of = [&](uint32_t t) -> uint32_t { return (seg_b + t) * 64 + lane; };
         bool hasA = wave < n_units, hasB = WPB + wave < n_units;      // wave-uniform
@@ -596,25 +518,7 @@ __global__ __launch_bounds__(kBatchDynBlock) void lbs_skin_batch_dyn(const LbsSe
         if (!first) __syncthreads();  // every wave is done with the previous segment's palette and ticket
         first = false;
         if (tid == 0) *ticket = 2 * WPB;
-        bool pj = false;
-#pragma unroll
-        for (int i = 0; i < PIECES; ++i) {
-            const uint32_t piece = my_piece + (uint32_t)i * kBatchDynBlock;
-            if (piece < n_pieces) {
-                const uint32_t b = piece >> 2, c = piece & 3;
-                float* r = reinterpret_cast<float*>(rows + b * 3);
-                *reinterpret_cast<f32x2*>(r + 2 * c) = f32x2{col[i].x, col[i].y};
-                r[8 + c] = col[i].z;
-                reinterpret_cast<float*>(row3 + b)[c] = col[i].w;
-                pj |= col[i].w != (c == 3 ? 1.0f : 0.0f);
-            }
-        }
-        const bool wave_pj = __any(pj) != 0;
-        if (lane == 0) wave_flag[wave] = wave_pj ? 1u : 0u;
-        __syncthreads();
-        bool projective = false;
-#pragma unroll
-        for (uint32_t wv = 0; wv < WPB; ++wv) projective |= wave_flag[wv] != 0;
+        const bool projective = block_projective<WPB>(pal.commit(a.n_bones, piece0, rows, row3), wave_flag, lane, wave);
         if (hasA) pin_vertex(A);
         if (hasB) B = load_vertex_buf<MASK, kDynLoadAux>(vb, vB);
 
@@ -625,9 +529,7 @@ __global__ __launch_bounds__(kBatchDynBlock) void lbs_skin_batch_dyn(const LbsSe
             store_vertex_buf<MASK, kDynStoreAux>(vb, v_c, o, c_.t.w);
         };
         auto refill = [&](VertexIn<MASK>& n_, uint32_t& v_n) -> bool {
-            uint32_t t = 0;
-            if (lane == 0) t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            t = __builtin_amdgcn_readfirstlane(t);
+            const uint32_t t = draw_ticket(ticket, lane);
             if (t >= n_units) return false;
             v_n = vertex_of(t);
             n_ = load_vertex_buf<MASK, kDynLoadAux>(vb, v_n);
@@ -735,13 +637,7 @@ __global__ __launch_bounds__(512) void lbs_skin_ex(LbsExArgs x, uint32_t units_p
         const uint32_t seg_e = (u_end < inst_u0 + units_per_inst ? u_end : inst_u0 + units_per_inst) - inst_u0;
         const PaletteRegs pr = palette_fetch(a.palette + (size_t)inst * a.n_bones * 16, a.n_bones, tid);
         if (inst != inst_first) __syncthreads();
-        const bool pj = palette_commit(pr, a.n_bones, rows, row3, tid);
-        const bool wave_pj = __any(pj) != 0;
-        if (lane == 0) wave_flag[wave] = wave_pj ? 1u : 0u;
-        __syncthreads();
-        bool projective = false;
-#pragma unroll
-        for (uint32_t wv = 0; wv < WPB; ++wv) projective |= wave_flag[wv] != 0;
+        const bool projective = block_projective<WPB>(palette_commit(pr, a.n_bones, rows, row3, tid), wave_flag, lane, wave);
         const float* sw = SHAPES ? x.shape_w + (size_t)inst * x.n_shapes : nullptr;
 
         for (uint32_t u = seg_b + wave; u < seg_e; u += WPB) {  // wave-uniform
@@ -924,13 +820,7 @@ __device__ __forceinline__ void aos_segment(const LbsExArgs& x, const float* __r
     if (vA) load_span(A, uA);
     if (!first) __syncthreads();   // every wave is done with the previous palette (and the previous segment's ticket)
     if (tid == 0) *ticket = (TWO ? 2 : 1) * WPB;
-    const bool pj = palette_commit(pr, a.n_bones, rows, row3, tid);
-    const bool wave_pj = __any(pj) != 0;
-    if (lane == 0) wave_flag[wave] = wave_pj ? 1u : 0u;
-    __syncthreads();
-    bool projective = false;
-#pragma unroll
-    for (uint32_t wv = 0; wv < WPB; ++wv) projective |= wave_flag[wv] != 0;
+    const bool projective = block_projective<WPB>(palette_commit(pr, a.n_bones, rows, row3, tid), wave_flag, lane, wave);
     if constexpr (TWO) if (vB) load_span(B, uB);     // (behind the staging barrier, as lbs_skin_dyn: the palette columns of the later waves do not queue behind it)
 
     // one unit: park the span in the slab, refill the register set, skin in the slab, stream the slab out
@@ -942,9 +832,7 @@ __device__ __forceinline__ void aos_segment(const LbsExArgs& x, const float* __r
         }
         const uint32_t u_now = u;
         {
-            uint32_t t = 0;
-            if (lane == 0) t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            t = __builtin_amdgcn_readfirstlane(t);
+            const uint32_t t = draw_ticket(ticket, lane);
             valid = t < n_units;
             u = seg_b + t;
             if (valid) load_span(r, u);
@@ -1466,13 +1354,9 @@ __global__ __launch_bounds__(256) void palette_kernel(const float* __restrict__ 
     const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n * 16) return;
     const uint32_t m = e >> 4, j = (e >> 2) & 3, i = e & 3;
-    const float* a = A + (size_t)m * 16;
-    const float* b = B + (size_t)m * 16;
-    float y = a[i] * b[j * 4];
-    y = a[4 + i] * b[j * 4 + 1] + y;
-    y = a[8 + i] * b[j * 4 + 2] + y;
-    y = a[12 + i] * b[j * 4 + 3] + y;
-    out[e] = y;
+    const float* a = A + (size_t)m * 16 + i;
+    const float* b = B + (size_t)m * 16 + j * 4;
+    out[e] = mat4_elem(f32x4{a[0], a[4], a[8], a[12]}, f32x4{b[0], b[1], b[2], b[3]});
 }
 
 hipError_t launch_palette(const float* d_global, const float* d_inv_bind, uint32_t n, float* d_out,

@@ -1,7 +1,8 @@
-// lbs_leaves.h -- the per-vertex device code of the skinning kernels: vector types, cache-policy loads / stores, palette staging into the
-// packed-math LDS layout, skin_vertex (the reference's operation order, see lbs_kernels.hip's head) and the vertex streams as
-// buffer resources.  Shared by lbs_kernels.hip (every skinning kernel) and anim_kernels.hip (the one-launch frame that goes on to
-// the vertices): ONE definition, so a vertex skinned inside a pose launch has the bits of one skinned by lbs_skin.
+// lbs_leaves.h -- the per-vertex device code of the skinning kernels: vector types, cache-policy loads / stores, the matrix product and
+// the bone palette column, palette staging into the packed-math LDS layout (with the affine test, the workgroup flag and the unit
+// ticket), skin_vertex (the reference's operation order, see lbs_kernels.hip's head) and the vertex streams as buffer resources.
+// Shared by lbs_kernels.hip (every skinning kernel) and anim_kernels.hip (the pose kernels' palettes, the one-launch frame that goes on
+// to the vertices): ONE definition, so a vertex skinned inside a pose launch has the bits of one skinned by lbs_skin.
 #pragma once
 #include "fyx_internal.h"
 
@@ -30,6 +31,27 @@ __device__ __forceinline__ void ld3(const float* p, float& x, float& y, float& z
 template <bool NT>
 __device__ __forceinline__ void st3(float* p, float x, float y, float z) {
     stg<NT>(p, x); stg<NT>(p + 1, y); stg<NT>(p + 2, z);
+}
+
+// nalgebra's Matrix4 * Matrix4, one element: a = row i of the left matrix, b = column j of the right one, summed as the
+// k-ascending axpy chain y = a0*b0; y = a1*b1 + y; ...  Every product of two matrices on the device (the hierarchy's walks,
+// the palettes global * inv_bind) is this chain.
+__device__ __forceinline__ float mat4_elem(f32x4 a, f32x4 b) {
+    float y = a.x * b.x;
+    y = a.y * b.y + y;
+    y = a.z * b.z + y;
+    y = a.w * b.w + y;
+    return y;
+}
+
+// Column c of bone_matrices[b] = global(node) * inv_bind(node) (scene/mesh/mod.rs:781-793): g = the node's four global
+// columns, ib = column c of its inverse bind matrix.  An invalid bone handle (node < 0) yields the identity's column.
+__device__ __forceinline__ f32x4 bone_palette_column(const f32x4* g, f32x4 ib, int32_t node, uint32_t c) {
+    if (node < 0) return f32x4{c == 0 ? 1.0f : 0.0f, c == 1 ? 1.0f : 0.0f, c == 2 ? 1.0f : 0.0f, c == 3 ? 1.0f : 0.0f};
+    const f32x4* a = g + (size_t)node * 4;
+    const f32x4 a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3];
+    return f32x4{mat4_elem(f32x4{a0.x, a1.x, a2.x, a3.x}, ib), mat4_elem(f32x4{a0.y, a1.y, a2.y, a3.y}, ib),
+                 mat4_elem(f32x4{a0.z, a1.z, a2.z, a3.z}, ib), mat4_elem(f32x4{a0.w, a1.w, a2.w, a3.w}, ib)};
 }
 
 // ---------------------------------------------------------------------------------------
@@ -64,15 +86,35 @@ __device__ __forceinline__ PaletteRegs palette_fetch(const float* __restrict__ p
     return r;
 }
 
-// Write the fetched bone to LDS in the packed-math layout; true if that matrix is projective.
+// The affine test of a matrix's last row (m30, m31, m32, m33) = (0, 0, 0, 1): one column's entry w = m3c, and the whole row.
+__device__ __forceinline__ bool column_projective(float w, uint32_t c) { return w != (c == 3 ? 1.0f : 0.0f); }
+__device__ __forceinline__ bool row3_projective(f32x4 w) { return !(w.x == 0.0f && w.y == 0.0f && w.z == 0.0f && w.w == 1.0f); }
+
+// Write column c = (m0c, m1c, m2c, m3c) of bone b into the packed-math layout: (x, y) is one 8-byte store, z and w one 4-byte
+// store each.  True if the column breaks the affine last row.
+__device__ __forceinline__ bool commit_column(f32x4* rows, f32x4* row3, uint32_t b, uint32_t c, f32x4 col) {
+    float* r = reinterpret_cast<float*>(rows + b * 3);
+    *reinterpret_cast<f32x2*>(r + 2 * c) = f32x2{col.x, col.y};
+    r[8 + c] = col.z;
+    reinterpret_cast<float*>(row3 + b)[c] = col.w;
+    return column_projective(col.w, c);
+}
+
+// Write a whole bone into the packed-math layout with whole-row stores; true if that matrix is projective.
+__device__ __forceinline__ bool commit_bone(const PaletteRegs& r, f32x4* rows, f32x4* row3, uint32_t b) {
+    rows[b * 3 + 0] = f32x4{r.c0.x, r.c0.y, r.c1.x, r.c1.y};
+    rows[b * 3 + 1] = f32x4{r.c2.x, r.c2.y, r.c3.x, r.c3.y};
+    rows[b * 3 + 2] = f32x4{r.c0.z, r.c1.z, r.c2.z, r.c3.z};
+    const f32x4 w = {r.c0.w, r.c1.w, r.c2.w, r.c3.w};
+    row3[b] = w;
+    return row3_projective(w);
+}
+
+// Write the fetched bone to LDS; true if that matrix is projective.
 __device__ __forceinline__ bool palette_commit(const PaletteRegs& r, uint32_t n_bones, f32x4* rows,
                                                f32x4* row3, int tid) {
     if ((uint32_t)tid >= n_bones) return false;
-    rows[tid * 3 + 0] = f32x4{r.c0.x, r.c0.y, r.c1.x, r.c1.y};
-    rows[tid * 3 + 1] = f32x4{r.c2.x, r.c2.y, r.c3.x, r.c3.y};
-    rows[tid * 3 + 2] = f32x4{r.c0.z, r.c1.z, r.c2.z, r.c3.z};
-    row3[tid] = f32x4{r.c0.w, r.c1.w, r.c2.w, r.c3.w};
-    return !(r.c0.w == 0.0f && r.c1.w == 0.0f && r.c2.w == 0.0f && r.c3.w == 1.0f);
+    return commit_bone(r, rows, row3, tid);
 }
 
 // Whole-palette staging by a workgroup of any size (AABB kernel).
@@ -81,14 +123,77 @@ __device__ __forceinline__ bool stage_palette(const float* __restrict__ pal, uin
     bool projective = false;
     for (uint32_t b = tid; b < n_bones; b += nthreads) {
         const f32x4* m = reinterpret_cast<const f32x4*>(pal + (size_t)b * 16);
-        f32x4 c0 = m[0], c1 = m[1], c2 = m[2], c3 = m[3];
-        rows[b * 3 + 0] = f32x4{c0.x, c0.y, c1.x, c1.y};
-        rows[b * 3 + 1] = f32x4{c2.x, c2.y, c3.x, c3.y};
-        rows[b * 3 + 2] = f32x4{c0.z, c1.z, c2.z, c3.z};
-        row3[b] = f32x4{c0.w, c1.w, c2.w, c3.w};
-        projective |= !(c0.w == 0.0f && c1.w == 0.0f && c2.w == 0.0f && c3.w == 1.0f);
+        projective |= commit_bone(PaletteRegs{m[0], m[1], m[2], m[3]}, rows, row3, b);
     }
     return projective;
+}
+
+// The dyn kernels' palette staging (n_bones <= 256): every thread of a BLOCK-thread workgroup fetches 1024 / BLOCK 16-byte
+// columns, the wave's FIRST vector-memory instruction; column c of bone b is piece 4 b + c, and a wave fetches 64 consecutive
+// pieces (16 bones, one dense 1 KB request).  WHICH lane takes which piece of those 64 is chosen for the LDS commit: the 16
+// lanes one ds_write_b64 serves together take the four columns of bones {0, 2, 4, 6} (or {1, 3, 5, 7}) of an octet, whose
+// 8-dword (x, y) windows at the 48-byte row stride start at dwords 0 / 24 / 48 / 72 = banks 0 / 24 / 16 / 8: the four windows
+// tile all 32 banks.  (With lanes in piece order the group was bones {0, 1, 2, 3}: windows at banks 0 / 12 / 24 / 4, the fourth
+// on top of the first -- SQ_LDS_BANK_CONFLICT 65 536 cycles per launch in round 2.)  The 32 lanes of a 4-byte store (z, w)
+// cover a whole octet of bones: dwords 12 b + 8 + c, all banks.
+// EMPTY_OK: the palette may have no bone at all (a batch segment), so no column is fetched.
+template <int BLOCK, bool EMPTY_OK = false>
+struct PaletteColumns {
+    static constexpr int kPieces = 1024 / BLOCK;
+    f32x4 col[kPieces];
+
+    __device__ __forceinline__ static uint32_t first_piece(uint32_t tid) {
+        const uint32_t lane = tid & 63, grp16 = lane >> 4, in16 = lane & 15;
+        return (tid & ~63u) + 4 * (8 * (grp16 >> 1) + 2 * (in16 >> 2) + (grp16 & 1)) + (in16 & 3);
+    }
+    __device__ __forceinline__ void fetch(const float* __restrict__ pal, uint32_t n_bones, uint32_t piece0) {
+        const uint32_t n_pieces = n_bones * 4;
+#pragma unroll
+        for (int i = 0; i < kPieces; ++i) {
+            const uint32_t piece = piece0 + (uint32_t)i * BLOCK;
+            const f32x4* p = reinterpret_cast<const f32x4*>(pal);
+            if constexpr (EMPTY_OK) col[i] = n_pieces ? p[piece < n_pieces ? piece : n_pieces - 1] : f32x4{0.f, 0.f, 0.f, 0.f};
+            else col[i] = p[piece < n_pieces ? piece : n_pieces - 1];
+        }
+    }
+    // true if a column this thread staged breaks the affine last row
+    __device__ __forceinline__ bool commit(uint32_t n_bones, uint32_t piece0, f32x4* rows, f32x4* row3) const {
+        const uint32_t n_pieces = n_bones * 4;
+        bool pj = false;
+#pragma unroll
+        for (int i = 0; i < kPieces; ++i) {
+            const uint32_t piece = piece0 + (uint32_t)i * BLOCK;
+            if (piece < n_pieces) pj |= commit_column(rows, row3, piece >> 2, piece & 3, col[i]);
+        }
+        return pj;
+    }
+};
+
+// Workgroup OR of the threads' projective flags, one LDS word per wave: publish the wave's bit, and after a barrier read the
+// workgroup's (block_projective: both around the barrier the palette staging needs anyway).
+__device__ __forceinline__ void publish_projective(bool pj, uint32_t* wave_flag, uint32_t lane, uint32_t wave) {
+    const bool wave_pj = __any(pj) != 0;
+    if (lane == 0) wave_flag[wave] = wave_pj ? 1u : 0u;
+}
+template <uint32_t WPB>
+__device__ __forceinline__ bool read_projective(const uint32_t* wave_flag) {
+    bool projective = false;
+#pragma unroll
+    for (uint32_t wv = 0; wv < WPB; ++wv) projective |= wave_flag[wv] != 0;
+    return projective;
+}
+template <uint32_t WPB>
+__device__ __forceinline__ bool block_projective(bool pj, uint32_t* wave_flag, uint32_t lane, uint32_t wave) {
+    publish_projective(pj, wave_flag, lane, wave);
+    __syncthreads();
+    return read_projective<WPB>(wave_flag);
+}
+
+// Draw a unit from the workgroup's LDS ticket counter: one ds_add_rtn per wave, the value wave-uniform.
+__device__ __forceinline__ uint32_t draw_ticket(uint32_t* ticket, uint32_t lane) {
+    uint32_t t = 0;
+    if (lane == 0) t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    return __builtin_amdgcn_readfirstlane(t);
 }
 
 // mat3 rows * v, reference order ((m0*x + m1*y) + m2*z); used by the projective normaliser.

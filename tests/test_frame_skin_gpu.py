@@ -58,9 +58,9 @@ def test_the_frame_that_skins_equals_update_then_lbs_skin(ctx, orc, make, n_inst
 
 @pytest.mark.parametrize("entry", [3, 7, 11, 15], ids=["m30", "m31", "m32", "m33"])
 def test_the_frame_that_skins_takes_the_homogeneous_path_for_any_entry_of_the_last_row(ctx, orc, entry):
-    """The skinning workgroups of the one-launch frame form their palette on chip and decide THERE whether a matrix is affine (their own
-    copy of the test, anim_kernels.hip frame_skin_body).  A bone whose inverse bind matrix has ONE non-affine entry in its last row gives a
-    palette matrix with exactly that last row (the global matrix's is (0, 0, 0, 1)): each entry alone must take the divide path --
+    """The skinning workgroups of the one-launch frame form their palette on chip and decide THERE whether a matrix is affine (the per-column
+    test of lbs_leaves.h, reached here through the frame's on-chip palette staging).  A bone whose inverse bind matrix has ONE non-affine
+    entry in its last row gives a palette matrix with exactly that last row (the global matrix's is (0, 0, 0, 1)): each entry alone must take the divide path --
     bit for bit what update + lbs_skin gives, and the oracle."""
     sc = cases.transitions()
     ib = np.tile(np.eye(4, dtype=np.float32).reshape(1, 16), (sc.rig.n_nodes, 1)) if sc.rig.inv_bind is None else np.array(sc.rig.inv_bind, np.float32).reshape(-1, 16)

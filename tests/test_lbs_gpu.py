@@ -484,10 +484,11 @@ def _nan_aware_equal(got, ref, what):
 def test_every_entry_of_the_last_row_decides_the_homogeneous_path(ctx, orc, entry, value):
     """Matrix4::transform_point divides by n = m30 x + m31 y + m32 z + m33 whenever n != 0 (nalgebra; scene/mesh/mod.rs:515-517): a matrix is
     affine for the kernels only if its last row is EXACTLY (0, 0, 0, 1), and each of the four entries alone must send it down the divide
-    path -- in every kernel's own copy of that test (tools/mutants.py, fourth batch: four of them ignored one entry each and the suite, whose
-    projective palettes always changed m30, m31 and m33 together, did not notice).  A last row of zeros makes n == 0: then nothing is divided
-    (a kernel that divides anyway writes inf / NaN).  lbs_skin, lbs_skin_dyn, the crowd kernel, both batched forms, the vertex-buffer kernel
-    and the two AABB kernels; every bit against the oracle."""
+    path -- through both definitions of that test in lbs_leaves.h, the whole-row one and the per-column one (tools/mutants.py, fourth batch:
+    four kernels' copies of them, since merged, each ignored one entry and the suite, whose projective palettes always changed m30, m31 and m33
+    together, did not notice).  A last row of zeros makes n == 0: then nothing is divided (a kernel that divides anyway writes inf / NaN).
+    lbs_skin, lbs_skin_dyn, the crowd kernel, both batched forms, the vertex-buffer kernel and the two AABB kernels each reach one of the two
+    definitions; every bit against the oracle."""
     nb = 12
     pal = synth.make_palette(nb, 5150).copy()
     pal[5, entry] = value                                       # (m33 = 0 on an otherwise affine matrix: the whole last row is zero, n == 0)
