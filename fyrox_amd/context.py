@@ -338,6 +338,17 @@ class Context:
                              out_stride, out_off_pos, out_off_normal, out_off_tangent)
         self._check(self._l.fyx_lbs_skin_ex(self._h, mesh_id, byref(d)))
 
+    def lbs_skin_ex_bounds(self, mesh_id: int, d_palette: int, n_bones: int, n_instances: int = 1, *,
+                           d_blend_shape_weights: int = 0, n_blend_shapes: int = 0, d_out_pos: int = 0,
+                           d_out_normal: int = 0, d_out_tangent: int = 0, d_out_vertices: int = 0, out_stride: int = 0,
+                           out_off_pos: int = -1, out_off_normal: int = -1, out_off_tangent: int = -1, d_out_aabb: int = 0) -> None:
+        """fyx_lbs_skin_ex_bounds: lbs_skin_ex plus every instance's box of skinned positions ({min xyz, max xyz} each) into
+        d_out_aabb, from the same launch.  Asynchronous."""
+        d = _native.SkinDesc(d_palette or None, n_bones, n_instances, d_blend_shape_weights or None, n_blend_shapes,
+                             d_out_pos or None, d_out_normal or None, d_out_tangent or None, d_out_vertices or None,
+                             out_stride, out_off_pos, out_off_normal, out_off_tangent)
+        self._check(self._l.fyx_lbs_skin_ex_bounds(self._h, mesh_id, byref(d), d_out_aabb or None))
+
     def lbs_skin_ex_batch(self, jobs) -> None:
         """fyx_lbs_skin_ex_batch.  jobs: sequence of (mesh_id, kwargs) with lbs_skin_ex's arguments
         (d_palette, n_bones, n_instances, d_blend_shape_weights, ...)."""

@@ -613,6 +613,39 @@ int build_ex_args(fyx_ctx* c, uint64_t mesh_id, const fyx_skin_desc* d, fyx::Lbs
     return FYX_OK;
 }
 
+// The slab of partial boxes for a bounds launch on stream `st` (BoundsOut::slab).  A slab that has to grow is freed once its stream
+// has drained; when every slot holds another stream's slab, all of them are, after a wait for everything in flight.
+struct BoundsSlabReq { fyx_ctx* c; hipStream_t st; };
+float* bounds_slab_for(void* user, size_t floats) {
+    BoundsSlabReq* r = static_cast<BoundsSlabReq*>(user);
+    fyx_ctx* c = r->c;
+    fyx_ctx::BoundsSlab* b = nullptr;
+    for (fyx_ctx::BoundsSlab& e : c->bounds_slab)
+        if (e.p && e.stream == r->st) { b = &e; break; }
+    if (!b) {
+        for (fyx_ctx::BoundsSlab& e : c->bounds_slab)
+            if (!e.p) { b = &e; break; }
+        if (!b) {
+            if (fyx::sync_all(c)) return nullptr;
+            for (fyx_ctx::BoundsSlab& e : c->bounds_slab) { (void)hipFree(e.p); e = fyx_ctx::BoundsSlab(); }
+            b = &c->bounds_slab[0];
+        }
+        b->stream = r->st;
+    }
+    if (b->floats < floats) {
+        if (b->p) {
+            if (hipStreamSynchronize(r->st) != hipSuccess) return nullptr;
+            (void)hipFree(b->p);
+            b->p = nullptr;
+            b->floats = 0;
+        }
+        const size_t want = std::max(floats, (size_t)64 * 1024);
+        if (hipMalloc(reinterpret_cast<void**>(&b->p), want * sizeof(float)) != hipSuccess) { b->p = nullptr; return nullptr; }
+        b->floats = want;
+    }
+    return b->p;
+}
+
 enum ExKind { kExWholeSpans, kExPlain, kExGeneral };
 ExKind ex_kind(const fyx::LbsExArgs& x, bool whole_spans) {
     if (whole_spans) return kExWholeSpans;
@@ -848,6 +881,8 @@ void fyx_shutdown(fyx_ctx* c) {
     for (auto& kv : c->meshes) free_mesh(kv.second);
     if (c->scratch) (void)hipFree(c->scratch);
     if (c->aabb_partials) (void)hipFree(c->aabb_partials);
+    for (fyx_ctx::BoundsSlab& b : c->bounds_slab)
+        if (b.p) { if (b.stream) (void)hipStreamSynchronize(b.stream); (void)hipFree(b.p); }
     if (c->d_u32) (void)hipFree(c->d_u32);
     if (c->dev_err) (void)hipHostFree(c->dev_err);
     for (hipEvent_t e : c->timing_ev) (void)hipEventDestroy(e);
@@ -1355,6 +1390,30 @@ int fyx_lbs_skin_ex(fyx_ctx* c, uint64_t mesh_id, const fyx_skin_desc* d) {
         case kExPlain: FYX_HIP(c, fyx::launch_lbs(x.a, c->lbs, st)); break;
         default: FYX_HIP(c, fyx::launch_lbs_ex(x, c->lbs, st)); break;
     }
+    return FYX_OK;
+    FYX_GUARD_END(c)
+}
+
+int fyx_lbs_skin_ex_bounds(fyx_ctx* c, uint64_t mesh_id, const fyx_skin_desc* d, float* d_out_aabb) {
+    if (!c) return FYX_ERR_INVALID_ARG;
+    FYX_GUARD_BEGIN
+    fyx::LbsExArgs x;
+    bool whole_spans = false;
+    if (int rc = build_ex_args(c, mesh_id, d, x, whole_spans)) return rc;
+    if (!d_out_aabb) return fail(c, FYX_ERR_INVALID_ARG, "d_out_aabb is null");
+    if (d->n_instances > 65535u) return fail(c, FYX_ERR_UNSUPPORTED, "at most 65535 instances per call");
+    hipStream_t st;
+    if (int sr = acquire_launch_stream(c, &st)) return sr;
+    BoundsSlabReq req{c, st};
+    const fyx::BoundsOut bo{bounds_slab_for, &req, d_out_aabb};
+    hipError_t e;
+    switch (ex_kind(x, whole_spans)) {
+        case kExWholeSpans: e = fyx::launch_lbs_aos_bounds(x, c->lbs, bo, st); break;
+        case kExPlain: e = fyx::launch_lbs_bounds(x.a, c->lbs, bo, st); break;
+        default: e = fyx::launch_lbs_ex_bounds(x, c->lbs, bo, st); break;
+    }
+    if (e == hipErrorOutOfMemory) return fail(c, FYX_ERR_OOM, "no device memory for the partial boxes");
+    FYX_HIP(c, e);
     return FYX_OK;
     FYX_GUARD_END(c)
 }

@@ -141,6 +141,11 @@ struct fyx_ctx {
     int plan_split = 2048;   // option "anim.split": instances per planning task
     fyx::PlanPool* plan_pool = nullptr;
     fyx::SkinBatch* skin_batch[2] = {nullptr, nullptr};     // two cached batches (the frames of the two frame streams skin from different palettes)
+    // Partial boxes of fyx_lbs_skin_ex_bounds, one slab per launch stream (consecutive calls alternate streams under lbs.streams = 2:
+    // a slab is reused only behind the previous call's fold on its own stream).  Grown on demand.
+    struct BoundsSlab { hipStream_t stream = nullptr; float* p = nullptr; size_t floats = 0; };
+    static constexpr int kBoundsSlabs = 8;
+    BoundsSlab bounds_slab[kBoundsSlabs];
     int skin_batch_last = 0;
 };
 

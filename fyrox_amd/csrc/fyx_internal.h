@@ -108,6 +108,17 @@ hipError_t launch_lbs_aos_batch(const LbsExSegDev* d_segs, uint32_t n_segs, cons
                                 const LbsTuning& t, hipStream_t stream);
 // whole-span variant: out = in with position / normal / tangent.xyz replaced; stride <= 160, multiple of 4
 hipError_t launch_lbs_aos(const LbsExArgs& x, const LbsTuning& t, hipStream_t stream);
+// Bounds forms (fyx_lbs_skin_ex_bounds): launch_lbs / launch_lbs_ex / launch_lbs_aos, plus out[n_instances][6] = each instance's box
+// of skinned positions {min xyz, max xyz}, folded by a second launch on the same stream from partial boxes in a slab that
+// slab(user, floats) hands out (null: hipErrorOutOfMemory).  The slab must not be in use by another stream meanwhile.
+struct BoundsOut {
+    float* (*slab)(void* user, size_t floats);
+    void* user;
+    float* out;
+};
+hipError_t launch_lbs_bounds(const LbsArgs& a, const LbsTuning& t, const BoundsOut& bo, hipStream_t stream);
+hipError_t launch_lbs_ex_bounds(const LbsExArgs& x, const LbsTuning& t, const BoundsOut& bo, hipStream_t stream);
+hipError_t launch_lbs_aos_bounds(const LbsExArgs& x, const LbsTuning& t, const BoundsOut& bo, hipStream_t stream);
 // engine RGB16F volume -> device tile layout (see lbs_kernels.hip)
 hipError_t launch_retile_blend_shapes(const uint16_t* d_src, uint32_t n_verts, uint32_t plane_vertices,
                                       uint32_t n_shapes, uint16_t* d_dst, hipStream_t stream);

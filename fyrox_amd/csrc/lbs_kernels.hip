@@ -66,10 +66,12 @@ constexpr int kSkinBlock = 512;   // threads per workgroup of lbs_skin / lbs_ski
 // first: no wave of the workgroup has used the LDS palette yet.  cur / nxt: the wave's two vertex register sets, owned by the
 // kernel so that they live across segments: declared in here, they gave some instantiations more VGPRs than the kernels had
 // before this body was shared -- lbs_skin<false, 2> 80 -> 82, one resident workgroup per CU fewer and 14 % slower.
-template <bool EXACT, int MASK>
+// BOX (lbs_skin_bounds): the segment's positions are also folded into a box, written to box_out (the LDS behind the wave flags holds
+// the workgroup's fold); CM = the streams loaded and skinned (positions always), MASK = the streams stored.
+template <bool EXACT, int MASK, bool BOX = false, int CM = MASK>
 __device__ __forceinline__ void skin_segment(const LbsArgs& a, const float* __restrict__ palette, size_t out_base, uint32_t seg_b,
-                                             uint32_t seg_e, bool first, unsigned char* smem, VertexIn<MASK>& cur,
-                                             VertexIn<MASK>& nxt) {
+                                             uint32_t seg_e, bool first, unsigned char* smem, VertexIn<CM>& cur,
+                                             VertexIn<CM>& nxt, float* box_out = nullptr) {
     constexpr bool NT = true;
     constexpr uint32_t WPB = kSkinBlock / 64;
     f32x4* rows = reinterpret_cast<f32x4*>(smem);
@@ -88,21 +90,25 @@ __device__ __forceinline__ void skin_segment(const LbsArgs& a, const float* __re
     constexpr uint32_t vstep = WPB * 64;
     uint32_t base = (seg_b + wave) * 64;
     uint32_t v = base + lane;
-    cur = load_vertex<NT, MASK>(a, v < ve ? v : 0);
+    cur = load_vertex<NT, CM>(a, v < ve ? v : 0);
 
     if (!first) __syncthreads();  // every wave is done with the previous palette
     const bool projective = block_projective<WPB>(palette_commit(pr, a.n_bones, rows, row3, tid), wave_flag, lane, wave);
     // Opaque use point: nothing that consumes the first unit's vertex data may be scheduled
     // above the staging barrier (it would drag the wait for those loads up with it).
     pin_vertex(cur);
+    BoxAcc box;
+    if constexpr (BOX) box.reset();
 
     while (base < ve) {  // wave-uniform
         const uint32_t bn = base + vstep;
         const uint32_t vn = bn + lane;
-        if (bn < ve) nxt = load_vertex<NT, MASK>(a, vn < ve ? vn : 0);
-        const Skinned o = skin_vertex<EXACT, MASK>(rows, row3, projective, cur.id, cur.w, cur.p.x,
-                                                   cur.p.y, cur.p.z, cur.n.x, cur.n.y, cur.n.z,
-                                                   cur.t.x, cur.t.y, cur.t.z);
+        if (bn < ve) nxt = load_vertex<NT, CM>(a, vn < ve ? vn : 0);
+        const Skinned o = skin_vertex<EXACT, CM>(rows, row3, projective, cur.id, cur.w, cur.p.x,
+                                                 cur.p.y, cur.p.z, cur.n.x, cur.n.y, cur.n.z,
+                                                 cur.t.x, cur.t.y, cur.t.z);
+        // (a lane past the segment skinned vertex 0 of the same instance: a point of this box already)
+        if constexpr (BOX) box.add(o.px, o.py, o.pz);
         if (v < ve) {
             const size_t ov = out_base + v;
             if constexpr (MASK & 1) st3<NT>(a.out_pos + ov * 3, o.px, o.py, o.pz);
@@ -114,6 +120,7 @@ __device__ __forceinline__ void skin_segment(const LbsArgs& a, const float* __re
         base = bn;
         v = vn;
     }
+    if constexpr (BOX) box_segment_end<kSkinBlock>(box, reinterpret_cast<float*>(wave_flag + 16), box_out, wave, lane);
 }
 
 template <bool EXACT, int MASK>
@@ -133,6 +140,31 @@ __global__ __launch_bounds__(kSkinBlock) void lbs_skin(LbsArgs a, uint32_t units
         const uint32_t seg_e = (u_end < inst_u0 + units_per_inst ? u_end : inst_u0 + units_per_inst) - inst_u0;
         skin_segment<EXACT, MASK>(a, a.palette + (size_t)inst * a.n_bones * 16, (size_t)inst * a.n_verts, seg_b, seg_e,
                                   inst == inst_first, smem, cur, nxt);
+    }
+}
+
+// The bounds forms (fyx_lbs_skin_ex_bounds) of the skinning kernels: the base kernel's loads, arithmetic and stores, plus a running
+// box of the positions per lane (positions are skinned even when MASK stores none) and one partial box per (workgroup, instance
+// segment) in box_slab; launch_bounds_fold then folds the partials of every instance.  Range kernels (the workgroup owns a contiguous
+// unit range, as here) write the segment of workgroup b and instance i at slot b + i: both grow along the unit numbering, so no two
+// segments share a slot.
+template <bool EXACT, int MASK>
+__global__ __launch_bounds__(kSkinBlock) void lbs_skin_bounds(LbsArgs a, uint32_t units_per_inst, uint32_t total_units, float* box_slab) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const uint32_t u_begin = (uint32_t)(((uint64_t)blockIdx.x * total_units) / gridDim.x);
+    const uint32_t u_end = (uint32_t)(((uint64_t)(blockIdx.x + 1) * total_units) / gridDim.x);
+    if (u_begin >= u_end) return;
+
+    VertexIn<MASK | 1> cur, nxt;
+    const uint32_t inst_first = u_begin / units_per_inst;
+    const uint32_t inst_last = (u_end - 1) / units_per_inst;
+
+    for (uint32_t inst = inst_first; inst <= inst_last; ++inst) {  // workgroup-uniform
+        const uint32_t inst_u0 = inst * units_per_inst;
+        const uint32_t seg_b = (u_begin > inst_u0 ? u_begin : inst_u0) - inst_u0;
+        const uint32_t seg_e = (u_end < inst_u0 + units_per_inst ? u_end : inst_u0 + units_per_inst) - inst_u0;
+        skin_segment<EXACT, MASK, true, MASK | 1>(a, a.palette + (size_t)inst * a.n_bones * 16, (size_t)inst * a.n_verts, seg_b, seg_e,
+                                                  inst == inst_first, smem, cur, nxt, box_slab + ((size_t)blockIdx.x + inst) * 6);
     }
 }
 
@@ -167,6 +199,64 @@ __global__ __launch_bounds__(kSkinBlock) void lbs_skin(LbsArgs a, uint32_t units
 // ---------------------------------------------------------------------------------------
 constexpr int kDynBlock = 256;
 constexpr int kDynLoadAux = 2, kDynStoreAux = 16;     // nt loads, sc1 stores
+
+// lbs_skin_dyn_bounds: a copy of lbs_skin_dyn's body (kept apart so that the base kernel's code stays as it was) that also folds
+// the positions into one box per workgroup.  CM = the streams loaded and skinned (positions always), MASK = the streams stored.
+template <bool EXACT, int MASK, int CM = MASK | 1>
+__device__ __forceinline__ void skin_dyn_body(const LbsArgs& a, uint32_t total_units, float* box_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    f32x4* rows = reinterpret_cast<f32x4*>(smem);
+    f32x4* row3 = rows + 3 * a.n_bones;
+    uint32_t* wave_flag = reinterpret_cast<uint32_t*>(row3 + a.n_bones);   // 16 words
+    uint32_t* ticket = wave_flag + 16;
+
+    constexpr uint32_t WPB = kDynBlock / 64;
+    const int tid = threadIdx.x;
+    const uint32_t lane = tid & 63, wave = tid >> 6;
+    const uint32_t u_begin = (uint32_t)(((uint64_t)blockIdx.x * total_units) / gridDim.x);
+    const uint32_t n_units = (uint32_t)(((uint64_t)(blockIdx.x + 1) * total_units) / gridDim.x) - u_begin;
+
+    // palette columns first (see PaletteColumns)
+    PaletteColumns<kDynBlock> pal;
+    const uint32_t piece0 = pal.first_piece(tid);
+    pal.fetch(a.palette, a.n_bones, piece0);
+    // the wave's first two units (tickets wave and WPB + wave; the launcher guarantees n_units >= 2 WPB)
+    const VtxBuffers vb = make_vtx_buffers(a);
+    auto vertex_of = [&](uint32_t t) -> uint32_t { return (u_begin + t) * 64 + lane; };
+    uint32_t vA = vertex_of(wave), vB = vertex_of(WPB + wave);
+    VertexIn<CM> A = load_vertex_buf<CM, kDynLoadAux>(vb, vA);
+    VertexIn<CM> B;   // requested behind the staging barrier (see above)
+
+    if (tid == 0) *ticket = 2 * WPB;
+    const bool projective = block_projective<WPB>(pal.commit(a.n_bones, piece0, rows, row3), wave_flag, lane, wave);
+    pin_vertex(A);
+    B = load_vertex_buf<CM, kDynLoadAux>(vb, vB);
+    BoxAcc box;
+    box.reset();
+
+    auto process = [&](VertexIn<CM>& c_, uint32_t v_c) {
+        pin_vertex(c_);   // the math's first touch of the loaded registers is here
+        const Skinned o = skin_vertex<EXACT, CM>(rows, row3, projective, c_.id, c_.w, c_.p.x, c_.p.y, c_.p.z,
+                                                 c_.n.x, c_.n.y, c_.n.z, c_.t.x, c_.t.y, c_.t.z);
+        if (v_c < a.n_verts) box.add(o.px, o.py, o.pz);   // (a lane past the mesh skinned zeros)
+        store_vertex_buf<MASK, kDynStoreAux>(vb, v_c, o, c_.t.w);
+    };
+    // draw the next unit into a register set whose math is done; false when the workgroup's range is used up
+    auto refill = [&](VertexIn<CM>& n_, uint32_t& v_n) -> bool {
+        const uint32_t t = draw_ticket(ticket, lane);
+        if (t >= n_units) return false;
+        v_n = vertex_of(t);
+        n_ = load_vertex_buf<CM, kDynLoadAux>(vb, v_n);
+        return true;
+    };
+    for (;;) {   // wave-uniform
+        process(A, vA);
+        if (!refill(A, vA)) { process(B, vB); break; }
+        process(B, vB);
+        if (!refill(B, vB)) { process(A, vA); break; }
+    }
+    box_segment_end<kDynBlock>(box, reinterpret_cast<float*>(ticket + 4), box_out, wave, lane);
+}
 
 template <bool EXACT, int MASK>
 __global__ __launch_bounds__(kDynBlock) void lbs_skin_dyn(LbsArgs a, uint32_t total_units) {
@@ -218,6 +308,12 @@ __global__ __launch_bounds__(kDynBlock) void lbs_skin_dyn(LbsArgs a, uint32_t to
         process(B, vB);
         if (!refill(B, vB)) { process(A, vA); break; }
     }
+}
+
+// one instance: workgroup b's partial box at slot b (see lbs_skin_bounds)
+template <bool EXACT, int MASK>
+__global__ __launch_bounds__(kDynBlock) void lbs_skin_dyn_bounds(LbsArgs a, uint32_t total_units, float* box_slab) {
+    skin_dyn_body<EXACT, MASK>(a, total_units, box_slab + (size_t)blockIdx.x * 6);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -320,6 +416,99 @@ __global__ __launch_bounds__(BLOCK) void lbs_skin_crowd(LbsArgs a, uint32_t tile
         }
         cur ^= 1;
     }
+}
+
+// lbs_skin_crowd_bounds: a copy of lbs_skin_crowd's body (kept apart so that the base kernel's code stays as it was).  Every thread skins
+// one vertex per instance, so the box is folded per instance: the thread's position goes to LDS right after its arithmetic (two
+// buffers, by instance parity), and after the NEXT instance's barrier -- the one the palette double buffer needs anyway -- one of waves
+// 4 - 7 (no bones: not the palette's loaders; they take turns) folds it into the partial box of (tile, instance) at slot
+// instance * tiles + tile; the last instance's after one more barrier.  CM / MASK as in skin_segment.
+template <int BLOCK, bool EXACT, int MASK, bool LEAN, int CM = MASK | 1>
+__device__ __forceinline__ void skin_crowd_body(const LbsArgs& a, uint32_t tiles, uint32_t ipb, unsigned char* smem, float* box_slab) {
+    const uint32_t buf_f4 = 4 * a.n_bones;  // rows (3 per bone) + row3 (1 per bone)
+    f32x4* const base = reinterpret_cast<f32x4*>(smem);
+    uint32_t* const flags = reinterpret_cast<uint32_t*>(base + 2 * buf_f4);  // [2][4]
+
+    const int tid = threadIdx.x;
+    const uint32_t lane = tid & 63, wave = tid >> 6;
+    // Workgroups are dealt round-robin over the 8 XCDs (each with its own L2) in blockIdx order, and all `tiles`
+    // workgroups of an instance run read the same palettes: ranked by (XCD, order within the XCD) instead of by blockIdx,
+    // consecutive ranks -- hence the workgroups of one instance run -- sit on ONE XCD, and a palette comes out of HBM
+    // once instead of once per XCD (PMC: 33 MB fetched per C3 launch for 4.7 MB of mesh and palettes).  Any permutation
+    // of the workgroups computes the same thing; only the placement is a guess about the hardware.
+    const uint32_t G = gridDim.x, x = blockIdx.x & 7u;
+    uint32_t rank = blockIdx.x >> 3;
+    for (uint32_t q = 0; q < x; ++q) rank += (G - q + 7u) >> 3;     // workgroups on the XCDs before this one
+    const uint32_t tile = rank % tiles, chunk = rank / tiles;
+    const uint32_t i0 = chunk * ipb;
+    const uint32_t i1 = (i0 + ipb < a.n_instances) ? i0 + ipb : a.n_instances;
+    if (i0 >= i1) return;
+    const uint32_t v = tile * BLOCK + tid;
+    const bool live = v < a.n_verts;
+
+    // Only the waves whose threads own a bone (n_bones <= 256: waves 0..3) take part in the palette traffic; each
+    // of those four waves owns one flag word per buffer (a wave without bones writes 0 there).
+    const bool owner = wave * 64 < a.n_bones;   // wave-uniform
+    PaletteRegs pr;
+    if (owner) pr = palette_fetch(a.palette + (size_t)i0 * a.n_bones * 16, a.n_bones, tid);
+    // the mesh is shared by every workgroup of the launch: ordinary (cacheable) loads
+    const VertexIn<CM> vin = load_vertex<false, CM>(a, live ? v : 0);
+    constexpr uint32_t kBoxBuf = (uint32_t)(box_lds_bytes<BLOCK>() / sizeof(float));
+    float* const box_lds = reinterpret_cast<float*>(flags + 2 * (BLOCK / 64));     // [2][kBoxBuf]
+    const uint32_t box_fold_wave = BLOCK / 64 - 4;   // + (instance & 3)
+    static_assert(BLOCK == 512, "the folding waves 4 - 7 own no bone only in 512-thread workgroups");
+    if (wave < 4) {
+        bool wave_pj = false;
+        if (owner) wave_pj = __any(palette_commit(pr, a.n_bones, base, base + 3 * a.n_bones, tid)) != 0;
+        if (lane == 0) flags[wave] = wave_pj ? 1u : 0u;
+    }
+    uint32_t cur = 0;
+    for (uint32_t inst = i0; inst < i1; ++inst) {  // workgroup-uniform
+        const bool more = inst + 1 < i1;
+        if (more && owner) pr = palette_fetch(a.palette + (size_t)(inst + 1) * a.n_bones * 16, a.n_bones, tid);
+        __syncthreads();  // buffer `cur` is complete; nobody reads buffer `cur ^ 1` any more
+        const f32x4* rows = base + cur * buf_f4;
+        const f32x4* row3 = rows + 3 * a.n_bones;
+        const u32x4 fl = *reinterpret_cast<const u32x4*>(flags + cur * 4);
+        const bool projective = (fl.x | fl.y | fl.z | fl.w) != 0;
+        if (inst > i0 && wave == box_fold_wave + ((inst - 1) & 3))
+            box_fold<BLOCK>(box_lds + (cur ^ 1) * kBoxBuf, box_slab + ((size_t)(inst - 1) * tiles + tile) * 6, lane);
+        // the crowd kernel is VALU-bound, so its fused mode blends the matrices first (see skin_vertex_blended)
+        const Skinned o = skin_vertex<EXACT, CM, true, LEAN>(rows, row3, projective, vin.id, vin.w, vin.p.x, vin.p.y,
+                                                             vin.p.z, vin.n.x, vin.n.y, vin.n.z, vin.t.x, vin.t.y, vin.t.z);
+        {
+            BoxAcc box;
+            box.reset();
+            if (live) box.add(o.px, o.py, o.pz);
+            box_put<BLOCK>(box, box_lds + cur * kBoxBuf, wave, lane);
+        }
+        if (live) {
+            const size_t ov = (size_t)inst * a.n_verts + v;
+            if constexpr (MASK & 1) st3<true>(a.out_pos + ov * 3, o.px, o.py, o.pz);
+            if constexpr (MASK & 2) st3<true>(a.out_nrm + ov * 3, o.nx, o.ny, o.nz);
+            if constexpr (MASK & 4)
+                stg<true>(reinterpret_cast<f32x4*>(a.out_tan) + ov, f32x4{o.tx, o.ty, o.tz, vin.t.w});
+        }
+        if (more && wave < 4) {
+            f32x4* nrows = base + (cur ^ 1) * buf_f4;
+            bool wave_pj = false;
+            if (owner) wave_pj = __any(palette_commit(pr, a.n_bones, nrows, nrows + 3 * a.n_bones, tid)) != 0;
+            if (lane == 0) flags[(cur ^ 1) * 4 + wave] = wave_pj ? 1u : 0u;
+        }
+        cur ^= 1;
+    }
+    __syncthreads();
+    if (wave == box_fold_wave + ((i1 - 1) & 3))
+        box_fold<BLOCK>(box_lds + (cur ^ 1) * kBoxBuf, box_slab + ((size_t)(i1 - 1) * tiles + tile) * 6, lane);
+}
+
+// LEAN is kept for the name's sake: the bounds launcher maps lbs.crowd_lean to the default form (LEAN = false).  Held to four waves per
+// SIMD (<= 128 VGPRs), the base kernel's occupancy; the exact form walks the influences one by one (skin_vertex's SEQ, as the lean
+// kernel does: the same operations per output component, the same bits) -- with all twelve rows live the box's few VGPRs spilled.
+template <int BLOCK, bool EXACT, int MASK, bool LEAN = false>
+__global__ __launch_bounds__(BLOCK, 4) void lbs_skin_crowd_bounds(LbsArgs a, uint32_t tiles, uint32_t ipb, float* box_slab) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    skin_crowd_body<BLOCK, EXACT, MASK, LEAN || EXACT>(a, tiles, ipb, smem, box_slab);
 }
 
 template <int BLOCK, bool EXACT, int MASK>
@@ -718,6 +907,134 @@ __global__ __launch_bounds__(512) void lbs_skin_ex(LbsExArgs x, uint32_t units_p
     }
 }
 
+
+// lbs_skin_ex_bounds: a copy of lbs_skin_ex's body (kept apart so that the base kernel's code stays as it was) that also folds the
+// positions into one box per (workgroup, instance segment); the LDS behind the wave flags holds the fold (see lbs_skin_bounds).
+template <bool EXACT, bool SHAPES, bool AOS>
+__device__ __forceinline__ void skin_ex_body(const LbsExArgs& x, uint32_t units_per_inst, uint32_t total_units, uint32_t slab_off,
+                                             unsigned char* smem, float* box_slab) {
+    const LbsArgs& a = x.a;
+    f32x4* rows = reinterpret_cast<f32x4*>(smem);
+    f32x4* row3 = rows + 3 * a.n_bones;
+    uint32_t* wave_flag = reinterpret_cast<uint32_t*>(row3 + a.n_bones);
+    constexpr uint32_t WPB = 512 / 64;
+    const int tid = threadIdx.x;
+    const uint32_t lane = tid & 63, wave = tid >> 6;
+    const uint32_t u_begin = (uint32_t)(((uint64_t)blockIdx.x * total_units) / gridDim.x);
+    const uint32_t u_end = (uint32_t)(((uint64_t)(blockIdx.x + 1) * total_units) / gridDim.x);
+    if (u_begin >= u_end) return;
+    const uint32_t inst_first = u_begin / units_per_inst, inst_last = (u_end - 1) / units_per_inst;
+    const bool has_n = a.nrm != nullptr, has_t = a.tan != nullptr;   // kernel-uniform
+    // the staged form's kernel-uniform facts: dwords per vertex, which of them are written, how the dword-in-vertex index of a lane moves
+    // from one 64-dword store to the next
+    const uint32_t spd = AOS ? x.out_stride / 4u : 1u;
+    uint64_t wmask = 0;
+    if constexpr (AOS) {
+        if (x.off_pos >= 0) wmask |= 7ull << (x.off_pos / 4);
+        if (has_n && x.off_nrm >= 0) wmask |= 7ull << (x.off_nrm / 4);
+        if (has_t && x.off_tan >= 0) wmask |= 15ull << (x.off_tan / 4);
+    }
+    const uint32_t f_step = 64u % spd, f_first = lane % spd;
+
+    for (uint32_t inst = inst_first; inst <= inst_last; ++inst) {
+        const uint32_t inst_u0 = inst * units_per_inst;
+        const uint32_t seg_b = (u_begin > inst_u0 ? u_begin : inst_u0) - inst_u0;
+        const uint32_t seg_e = (u_end < inst_u0 + units_per_inst ? u_end : inst_u0 + units_per_inst) - inst_u0;
+        const PaletteRegs pr = palette_fetch(a.palette + (size_t)inst * a.n_bones * 16, a.n_bones, tid);
+        if (inst != inst_first) __syncthreads();
+        const bool projective = block_projective<WPB>(palette_commit(pr, a.n_bones, rows, row3, tid), wave_flag, lane, wave);
+        const float* sw = SHAPES ? x.shape_w + (size_t)inst * x.n_shapes : nullptr;
+        BoxAcc box;
+        box.reset();
+
+        for (uint32_t u = seg_b + wave; u < seg_e; u += WPB) {  // wave-uniform
+            const uint32_t v = u * 64 + lane;
+            const uint32_t vs = v < a.n_verts ? v : 0;
+            float px, py, pz, nx = 0.f, ny = 0.f, nz = 0.f;
+            f32x4 t = {0.f, 0.f, 0.f, 0.f};
+            ld3<true>(a.pos + (size_t)vs * 3, px, py, pz);
+            if (has_n) ld3<true>(a.nrm + (size_t)vs * 3, nx, ny, nz);
+            if (has_t) t = ldg<true>(reinterpret_cast<const f32x4*>(a.tan) + vs);
+            const f32x4 w = ldg<true>(reinterpret_cast<const f32x4*>(a.wgt) + vs);
+            const uint32_t id = ldg<true>(a.idx + vs);
+            if constexpr (SHAPES) {
+                // tile u of every shape: 9 planes of 64 halfs; this lane's column
+                const uint16_t* col = x.shapes + ((size_t)u * 9) * 64 + lane;
+                const size_t shape_stride = (size_t)x.tiles_per_shape * 9 * 64;
+#pragma unroll 2
+                for (uint32_t sidx = 0; sidx < x.n_shapes; ++sidx) {
+                    const uint16_t* c = col + (size_t)sidx * shape_stride;
+                    const float ws = sw[sidx];
+                    uint16_t h[9];
+#pragma unroll
+                    for (int k = 0; k < 9; ++k) h[k] = __builtin_nontemporal_load(c + k * 64);
+                    if constexpr (EXACT) {
+                        px = px + h2f(h[0]) * ws; py = py + h2f(h[1]) * ws; pz = pz + h2f(h[2]) * ws;
+                        nx = nx + h2f(h[3]) * ws; ny = ny + h2f(h[4]) * ws; nz = nz + h2f(h[5]) * ws;
+                        t.x = t.x + h2f(h[6]) * ws; t.y = t.y + h2f(h[7]) * ws; t.z = t.z + h2f(h[8]) * ws;
+                    } else {
+                        px = __builtin_fmaf(h2f(h[0]), ws, px); py = __builtin_fmaf(h2f(h[1]), ws, py);
+                        pz = __builtin_fmaf(h2f(h[2]), ws, pz); nx = __builtin_fmaf(h2f(h[3]), ws, nx);
+                        ny = __builtin_fmaf(h2f(h[4]), ws, ny); nz = __builtin_fmaf(h2f(h[5]), ws, nz);
+                        t.x = __builtin_fmaf(h2f(h[6]), ws, t.x); t.y = __builtin_fmaf(h2f(h[7]), ws, t.y);
+                        t.z = __builtin_fmaf(h2f(h[8]), ws, t.z);
+                    }
+                }
+            }
+            const Skinned o = skin_vertex<EXACT, 7>(rows, row3, projective, id, w, px, py, pz, nx, ny, nz, t.x, t.y, t.z);
+            if (v < a.n_verts) box.add(o.px, o.py, o.pz);
+            if constexpr (AOS) {
+                if (slab_off) {      // kernel-uniform
+                    unsigned char* slab = smem + slab_off + (size_t)wave * 64 * x.out_stride;
+                    unsigned char* rec = slab + (size_t)lane * x.out_stride;       // (stride / 4 is odd for the engine's layouts: no bank conflicts)
+                    if (x.off_pos >= 0) { float* q = reinterpret_cast<float*>(rec + x.off_pos); q[0] = o.px; q[1] = o.py; q[2] = o.pz; }
+                    if (has_n && x.off_nrm >= 0) { float* q = reinterpret_cast<float*>(rec + x.off_nrm); q[0] = o.nx; q[1] = o.ny; q[2] = o.nz; }
+                    if (has_t && x.off_tan >= 0) { float* q = reinterpret_cast<float*>(rec + x.off_tan); q[0] = o.tx; q[1] = o.ty; q[2] = o.tz; q[3] = t.w; }
+                    __builtin_amdgcn_wave_barrier();      // a slab belongs to one wave, whose LDS operations complete in order
+                    const uint32_t n_valid = (a.n_verts - u * 64) < 64u ? (a.n_verts - u * 64) : 64u;
+                    const uint32_t n_dw = n_valid * spd;
+                    const uint32_t* s32 = reinterpret_cast<const uint32_t*>(slab);
+                    uint32_t* o32 = reinterpret_cast<uint32_t*>(x.out_aos + ((size_t)inst * a.n_verts + (size_t)u * 64) * x.out_stride);
+                    uint32_t f = f_first;
+                    for (uint32_t d = lane; d < n_dw; d += 64) {
+                        if ((wmask >> f) & 1ull) o32[d] = s32[d];      // (cacheable: nt stores measured the same at 68 bytes and 10 % slower at 48)
+                        f += f_step;
+                        if (f >= spd) f -= spd;
+                    }
+                    __builtin_amdgcn_wave_barrier();      // the slab is rewritten by the wave's next unit
+                    continue;
+                }
+            }
+            if (v < a.n_verts) {
+                const size_t ov = (size_t)inst * a.n_verts + v;
+                if constexpr (AOS) {
+                    unsigned char* rec = x.out_aos + ov * x.out_stride;
+                    if (x.off_pos >= 0) st3<true>(reinterpret_cast<float*>(rec + x.off_pos), o.px, o.py, o.pz);
+                    if (has_n && x.off_nrm >= 0) st3<true>(reinterpret_cast<float*>(rec + x.off_nrm), o.nx, o.ny, o.nz);
+                    if (has_t && x.off_tan >= 0) {
+                        float* tp = reinterpret_cast<float*>(rec + x.off_tan);
+                        st3<true>(tp, o.tx, o.ty, o.tz);
+                        stg<true>(tp + 3, t.w);
+                    }
+                } else {
+                    if (a.out_pos) st3<true>(a.out_pos + ov * 3, o.px, o.py, o.pz);
+                    if (a.out_nrm) st3<true>(a.out_nrm + ov * 3, o.nx, o.ny, o.nz);
+                    if (a.out_tan) stg<true>(reinterpret_cast<f32x4*>(a.out_tan) + ov, f32x4{o.tx, o.ty, o.tz, t.w});
+                }
+            }
+        }
+        box_segment_end<512>(box, reinterpret_cast<float*>(wave_flag + 16), box_slab + ((size_t)blockIdx.x + inst) * 6, wave, lane);
+    }
+}
+
+// range kernel: slot b + i (see lbs_skin_bounds); the staged interleaved form's slabs lie behind the box's LDS
+template <bool EXACT, bool SHAPES, bool AOS>
+__global__ __launch_bounds__(512) void lbs_skin_ex_bounds(LbsExArgs x, uint32_t units_per_inst, uint32_t total_units, uint32_t slab_off,
+                                                          float* box_slab) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    skin_ex_body<EXACT, SHAPES, AOS>(x, units_per_inst, total_units, slab_off, smem, box_slab);
+}
+
 template <bool EXACT, bool SHAPES, bool AOS>
 static hipError_t launch_ex_one(const LbsExArgs& x, const LbsTuning& t, hipStream_t s) {
     const uint32_t upi = (x.a.n_verts + 63) / 64;
@@ -781,10 +1098,12 @@ constexpr int kAosBlock = 256;
 // One segment (= the units [seg_b, seg_e) of one instance of one mesh) of the whole-span kernel: shared by the
 // single-mesh launch (segments = the instances of x) and the batched one (segments = the batch's table).
 // palette / sw / out_inst: this instance's matrices, blend-shape weights and output vertex buffer.
-template <bool EXACT, bool SHAPES, uint32_t PL>
+// BOX (lbs_skin_aos_bounds): the segment's positions are also folded into a box, written to box_out (the LDS behind the slabs holds
+// the workgroup's fold).
+template <bool EXACT, bool SHAPES, uint32_t PL, bool BOX = false>
 __device__ __forceinline__ void aos_segment(const LbsExArgs& x, const float* __restrict__ palette, const float* __restrict__ sw,
                                             unsigned char* __restrict__ out_inst, uint32_t seg_b, uint32_t seg_e, bool first,
-                                            unsigned char* smem) {
+                                            unsigned char* smem, float* box_out = nullptr) {
     const LbsArgs& a = x.a;
     f32x4* rows = reinterpret_cast<f32x4*>(smem);
     f32x4* row3 = rows + 3 * a.n_bones;
@@ -822,6 +1141,8 @@ __device__ __forceinline__ void aos_segment(const LbsExArgs& x, const float* __r
     if (tid == 0) *ticket = (TWO ? 2 : 1) * WPB;
     const bool projective = block_projective<WPB>(palette_commit(pr, a.n_bones, rows, row3, tid), wave_flag, lane, wave);
     if constexpr (TWO) if (vB) load_span(B, uB);     // (behind the staging barrier, as lbs_skin_dyn: the palette columns of the later waves do not queue behind it)
+    BoxAcc box;
+    if constexpr (BOX) box.reset();
 
     // one unit: park the span in the slab, refill the register set, skin in the slab, stream the slab out
     auto process = [&](f32x4 (&r)[PL], uint32_t& u, bool& valid) {
@@ -874,6 +1195,7 @@ __device__ __forceinline__ void aos_segment(const LbsExArgs& x, const float* __r
             }
         }
         const Skinned o = skin_vertex<EXACT, 7>(rows, row3, projective, id, w, px, py, pz, nx, ny, nz, t.x, t.y, t.z);
+        if constexpr (BOX) if (a.n_verts - u_now * 64 > lane) box.add(o.px, o.py, o.pz);   // (whole vertices of a ragged last unit)
         pp[0] = o.px; pp[1] = o.py; pp[2] = o.pz;
         if (np_) { np_[0] = o.nx; np_[1] = o.ny; np_[2] = o.nz; }
         if (tp) { tp[0] = o.tx; tp[1] = o.ty; tp[2] = o.tz; }
@@ -906,6 +1228,9 @@ __device__ __forceinline__ void aos_segment(const LbsExArgs& x, const float* __r
             process(B, uB, vB);
         }
     }
+    if constexpr (BOX)
+        box_segment_end<kAosBlock>(box, reinterpret_cast<float*>(smem + (size_t)a.n_bones * 64 + 64 + (size_t)WPB * 64 * stride), box_out,
+                                   wave, lane);
 }
 
 template <bool EXACT, bool SHAPES, uint32_t PL>
@@ -923,6 +1248,27 @@ __global__ __launch_bounds__(kAosBlock, (SHAPES && PL <= 5) ? 4 : 1) void lbs_sk
         aos_segment<EXACT, SHAPES, PL>(x, a.palette + (size_t)inst * a.n_bones * 16,
                                        SHAPES ? x.shape_w + (size_t)inst * x.n_shapes : nullptr,
                                        x.out_aos + (size_t)inst * a.n_verts * x.out_stride, seg_b, seg_e, inst == inst_first, smem);
+    }
+}
+
+// range kernel: slot b + i (see lbs_skin_bounds)
+template <bool EXACT, bool SHAPES, uint32_t PL>
+__global__ __launch_bounds__(kAosBlock, (SHAPES && PL <= 5) ? 4 : 1) void lbs_skin_aos_bounds(LbsExArgs x, uint32_t units_per_inst, uint32_t total_units,
+                                                                                            float* box_slab) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const LbsArgs& a = x.a;
+    const uint32_t u_begin = (uint32_t)(((uint64_t)blockIdx.x * total_units) / gridDim.x);
+    const uint32_t u_end = (uint32_t)(((uint64_t)(blockIdx.x + 1) * total_units) / gridDim.x);
+    if (u_begin >= u_end) return;
+    const uint32_t inst_first = u_begin / units_per_inst, inst_last = (u_end - 1) / units_per_inst;
+    for (uint32_t inst = inst_first; inst <= inst_last; ++inst) {
+        const uint32_t inst_u0 = inst * units_per_inst;
+        const uint32_t seg_b = (u_begin > inst_u0 ? u_begin : inst_u0) - inst_u0;
+        const uint32_t seg_e = (u_end < inst_u0 + units_per_inst ? u_end : inst_u0 + units_per_inst) - inst_u0;
+        aos_segment<EXACT, SHAPES, PL, true>(x, a.palette + (size_t)inst * a.n_bones * 16,
+                                             SHAPES ? x.shape_w + (size_t)inst * x.n_shapes : nullptr,
+                                             x.out_aos + (size_t)inst * a.n_verts * x.out_stride, seg_b, seg_e, inst == inst_first, smem,
+                                             box_slab + ((size_t)blockIdx.x + inst) * 6);
     }
 }
 
@@ -1342,6 +1688,221 @@ hipError_t launch_points_aabb(const float* d_xyz, uint64_t n_points, float* d_pa
                        d_partials);
     hipLaunchKernelGGL(aabb_final_kernel, dim3(1), dim3(kAabbBlock), 0, s, d_partials, grid, d_out);
     return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// Bounds forms (fyx_lbs_skin_ex_bounds): the skinning launch writes one partial box per (workgroup, instance segment) into a slab
+// the caller owns per launch stream, and bounds_fold_kernel folds each instance's partials into its box, behind it on the same
+// stream.  (No global float atomics, no last-arriver fold: the partials cross XCDs, whose L2s are not coherent with each other, and
+// the kernel boundary orders them.)  Which kernel skins is decided as in launch_lbs / launch_lbs_ex / launch_lbs_aos, except that
+// lbs.crowd_lean takes the default crowd form.
+// ---------------------------------------------------------------------------------------
+// Instance blockIdx.x's box from the slab: range partials (tiles == 0: workgroup b of `grid` over `total` units, upi units per
+// instance, wrote its segment of instance i at slot b + i) or tiled ones (slot i * tiles + t).  An instance without partials (an
+// empty mesh) gets the default box (+MAX, -MAX).  256 threads: the one instance of a large mesh has ~1000 partials to read.
+__global__ __launch_bounds__(kAabbBlock) void bounds_fold_kernel(const float* __restrict__ slab, uint32_t tiles, uint32_t grid, uint32_t total,
+                                                                 uint32_t upi, float* __restrict__ out) {
+    const uint32_t inst = blockIdx.x;
+    float mn[3] = {__FLT_MAX__, __FLT_MAX__, __FLT_MAX__};
+    float mx[3] = {-__FLT_MAX__, -__FLT_MAX__, -__FLT_MAX__};
+    size_t s0 = 0, s1 = 0;      // the instance's slots [s0, s1)
+    if (tiles) {
+        s0 = (size_t)inst * tiles;
+        s1 = s0 + tiles;
+    } else if (total) {
+        // the workgroups whose range [u_begin(b), u_end(b)) meets the instance's units [U0, U1): u_end(b) > U0 <=> b >= ceil((U0 + 1) G / T)
+        // - 1, u_begin(b) < U1 <=> b <= ceil(U1 G / T) - 1.  Every launcher's grid is at most its unit count, so no range is empty and
+        // each of those workgroups wrote a partial.
+        const uint64_t U0 = (uint64_t)inst * upi, U1 = U0 + upi, G = grid, T = total;
+        const uint64_t b0 = ((U0 + 1) * G + T - 1) / T - 1, b1 = (U1 * G + T - 1) / T - 1;
+        s0 = (size_t)b0 + inst;
+        s1 = (size_t)(b1 < G ? b1 : G - 1) + inst + 1;
+    }
+    for (size_t sl = s0 + threadIdx.x; sl < s1; sl += kAabbBlock) {
+        const float* q = slab + sl * 6;
+        for (int i = 0; i < 3; ++i) { mn[i] = fminf(mn[i], q[i]); mx[i] = fmaxf(mx[i], q[3 + i]); }
+    }
+    block_minmax_store(mn, mx, out + (size_t)inst * 6);
+}
+
+static hipError_t launch_bounds_fold(const float* slab, uint32_t n_instances, uint32_t tiles, uint32_t grid, uint32_t total, uint32_t upi,
+                                     float* out, hipStream_t s) {
+    hipLaunchKernelGGL(bounds_fold_kernel, dim3(n_instances), dim3(kAabbBlock), 0, s, slab, tiles, grid, total, upi, out);
+    return hipGetLastError();
+}
+
+static size_t range_slab_floats(uint32_t grid, uint32_t n_instances) { return ((size_t)grid + n_instances) * 6; }
+
+template <bool EXACT, int MASK>
+static hipError_t launch_bounds_skin(const LbsArgs& a, const LbsTuning& t, const BoundsOut& bo, hipStream_t s) {
+    const uint32_t upi = (a.n_verts + 63) / 64;
+    const uint64_t total64 = (uint64_t)upi * a.n_instances;
+    if (total64 > 0xffffffffull) return hipErrorInvalidValue;
+    const uint32_t total = (uint32_t)total64;
+    uint32_t grid = (uint32_t)kCUs * (uint32_t)(t.blocks_per_cu > 0 ? t.blocks_per_cu : 1);
+    const uint32_t max_useful = (total + (kSkinBlock / 64) - 1) / (kSkinBlock / 64);
+    if (grid > max_useful) grid = max_useful;
+    float* slab = bo.slab(bo.user, range_slab_floats(grid, a.n_instances));
+    if (!slab) return hipErrorOutOfMemory;
+    const size_t lds = (size_t)a.n_bones * 64 + 64 + box_lds_bytes<kSkinBlock>();
+    hipLaunchKernelGGL((lbs_skin_bounds<EXACT, MASK>), dim3(grid), dim3(kSkinBlock), (uint32_t)lds, s, a, upi, total, slab);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    return launch_bounds_fold(slab, a.n_instances, 0, grid, total, upi, bo.out, s);
+}
+
+// hipErrorNotReady: the launch does not qualify for lbs_skin_dyn (as launch_dyn_one)
+template <bool EXACT, int MASK>
+static hipError_t launch_bounds_dyn(const LbsArgs& a, const BoundsOut& bo, hipStream_t s) {
+    constexpr uint32_t WPB = kDynBlock / 64;
+    const uint32_t total = (a.n_verts + 63) / 64;
+    const uint32_t grid = (uint32_t)kCUs * (1024u / kDynBlock);
+    if (total / grid < 2 * WPB) return hipErrorNotReady;
+    float* slab = bo.slab(bo.user, range_slab_floats(grid, 1));
+    if (!slab) return hipErrorOutOfMemory;
+    const size_t lds = (size_t)a.n_bones * 64 + 64 + 16 + box_lds_bytes<kDynBlock>();
+    hipLaunchKernelGGL((lbs_skin_dyn_bounds<EXACT, MASK>), dim3(grid), dim3(kDynBlock), (uint32_t)lds, s, a, total, slab);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    return launch_bounds_fold(slab, 1, 0, grid, total, total, bo.out, s);
+}
+
+template <bool EXACT, int MASK>
+static hipError_t launch_bounds_crowd(const LbsArgs& a, const LbsTuning& t, const BoundsOut& bo, hipStream_t s) {
+    constexpr int BLOCK = kSkinBlock;
+    const uint32_t tiles = (a.n_verts + BLOCK - 1) / BLOCK;
+    uint32_t ipb = (uint32_t)(t.crowd_ipb > 0 ? t.crowd_ipb : 0);
+    if (ipb == 0) {     // launch_crowd_one's choice
+        const uint64_t pairs = (uint64_t)tiles * a.n_instances;
+        uint64_t want = pairs / ((uint64_t)kCUs * 4);
+        if (want < 1) want = 1;
+        if (want > 8u) want = 8u;
+        ipb = (uint32_t)want;
+    }
+    if (ipb > a.n_instances) ipb = a.n_instances;
+    const uint32_t chunks = (a.n_instances + ipb - 1) / ipb;
+    const uint64_t grid = (uint64_t)tiles * chunks;
+    if (grid > 0x7fffffffull) return hipErrorInvalidValue;
+    float* slab = bo.slab(bo.user, (size_t)a.n_instances * tiles * 6);
+    if (!slab) return hipErrorOutOfMemory;
+    const size_t lds = (size_t)a.n_bones * 64 * 2 + 2 * (BLOCK / 64) * sizeof(uint32_t) + 2 * box_lds_bytes<BLOCK>();
+    hipLaunchKernelGGL((lbs_skin_crowd_bounds<BLOCK, EXACT, MASK>), dim3((uint32_t)grid), dim3(BLOCK), (uint32_t)lds, s, a, tiles, ipb, slab);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    return launch_bounds_fold(slab, a.n_instances, tiles, 0, 0, 0, bo.out, s);
+}
+
+template <bool EXACT, int MASK>
+static hipError_t launch_bounds_plain_one(const LbsArgs& a, const LbsTuning& t, const BoundsOut& bo, hipStream_t s) {
+    if (t.dyn && a.n_instances == 1 && a.n_bones != 0 && a.n_bones <= 256 && a.n_verts <= 0x0fffffffu) {
+        const hipError_t e = launch_bounds_dyn<EXACT, MASK>(a, bo, s);
+        if (e != hipErrorNotReady) return e;
+    }
+    if (t.crowd > 0 || (t.crowd < 0 && a.n_instances >= 4)) return launch_bounds_crowd<EXACT, MASK>(a, t, bo, s);
+    return launch_bounds_skin<EXACT, MASK>(a, t, bo, s);
+}
+
+template <bool EXACT>
+static hipError_t launch_bounds_plain_mask(const LbsArgs& a, const LbsTuning& t, const BoundsOut& bo, hipStream_t s) {
+    // (mask 0, nothing stored, still skins the positions for the box)
+    const int mask = (a.out_pos ? 1 : 0) | ((a.out_nrm && a.nrm) ? 2 : 0) | ((a.out_tan && a.tan) ? 4 : 0);
+    switch (mask) {
+        case 0: return launch_bounds_plain_one<EXACT, 0>(a, t, bo, s);
+        case 1: return launch_bounds_plain_one<EXACT, 1>(a, t, bo, s);
+        case 2: return launch_bounds_plain_one<EXACT, 2>(a, t, bo, s);
+        case 3: return launch_bounds_plain_one<EXACT, 3>(a, t, bo, s);
+        case 4: return launch_bounds_plain_one<EXACT, 4>(a, t, bo, s);
+        case 5: return launch_bounds_plain_one<EXACT, 5>(a, t, bo, s);
+        case 6: return launch_bounds_plain_one<EXACT, 6>(a, t, bo, s);
+        default: return launch_bounds_plain_one<EXACT, 7>(a, t, bo, s);
+    }
+}
+
+hipError_t launch_lbs_bounds(const LbsArgs& a, const LbsTuning& t, const BoundsOut& bo, hipStream_t s) {
+    if (a.n_instances == 0) return hipSuccess;
+    if (a.n_verts == 0) return launch_bounds_fold(nullptr, a.n_instances, 0, 0, 0, 0, bo.out, s);
+    return t.exact ? launch_bounds_plain_mask<true>(a, t, bo, s) : launch_bounds_plain_mask<false>(a, t, bo, s);
+}
+
+template <bool EXACT, bool SHAPES, bool AOS>
+static hipError_t launch_bounds_ex_one(const LbsExArgs& x, const BoundsOut& bo, hipStream_t s) {
+    const uint32_t upi = (x.a.n_verts + 63) / 64;
+    const uint64_t total64 = (uint64_t)upi * x.a.n_instances;
+    if (total64 > 0xffffffffull) return hipErrorInvalidValue;
+    const uint32_t total = (uint32_t)total64;
+    uint32_t grid = (uint32_t)kCUs * 2u;      // launch_ex_one's grid
+    const uint32_t max_useful = (total + 7) / 8;
+    if (grid > max_useful) grid = max_useful;
+    float* slab = bo.slab(bo.user, range_slab_floats(grid, x.a.n_instances));
+    if (!slab) return hipErrorOutOfMemory;
+    size_t lds = (size_t)x.a.n_bones * 64 + 64 + box_lds_bytes<512>();
+    uint32_t slab_off = 0;
+    if (AOS && x.out_stride >= 4 && x.out_stride <= 160) {
+        slab_off = (uint32_t)lds;
+        lds += (size_t)8 * 64 * x.out_stride;
+    }
+    if (lds > 64 * 1024) {
+        if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lbs_skin_ex_bounds<EXACT, SHAPES, AOS>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((lbs_skin_ex_bounds<EXACT, SHAPES, AOS>), dim3(grid), dim3(512), lds, s, x, upi, total, slab_off, slab);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    return launch_bounds_fold(slab, x.a.n_instances, 0, grid, total, upi, bo.out, s);
+}
+
+hipError_t launch_lbs_ex_bounds(const LbsExArgs& x, const LbsTuning& t, const BoundsOut& bo, hipStream_t s) {
+    if (x.a.n_instances == 0) return hipSuccess;
+    if (x.a.n_verts == 0) return launch_bounds_fold(nullptr, x.a.n_instances, 0, 0, 0, 0, bo.out, s);
+    const bool shapes = x.n_shapes > 0, aos = x.out_aos != nullptr;
+    const int key = (t.exact ? 4 : 0) | (shapes ? 2 : 0) | (aos ? 1 : 0);
+    switch (key) {
+        case 7: return launch_bounds_ex_one<true, true, true>(x, bo, s);
+        case 6: return launch_bounds_ex_one<true, true, false>(x, bo, s);
+        case 5: return launch_bounds_ex_one<true, false, true>(x, bo, s);
+        case 4: return launch_bounds_ex_one<true, false, false>(x, bo, s);
+        case 3: return launch_bounds_ex_one<false, true, true>(x, bo, s);
+        case 2: return launch_bounds_ex_one<false, true, false>(x, bo, s);
+        case 1: return launch_bounds_ex_one<false, false, true>(x, bo, s);
+        default: return launch_bounds_ex_one<false, false, false>(x, bo, s);
+    }
+}
+
+template <bool EXACT, bool SHAPES, uint32_t PL>
+static hipError_t launch_bounds_aos_pl(const LbsExArgs& x, const BoundsOut& bo, hipStream_t s) {
+    const uint32_t upi = (x.a.n_verts + 63) / 64;
+    const uint64_t total64 = (uint64_t)upi * x.a.n_instances;
+    if (total64 > 0xffffffffull) return hipErrorInvalidValue;
+    const uint32_t total = (uint32_t)total64;
+    constexpr uint32_t WPB = kAosBlock / 64;
+    const size_t lds = aos_lds_bytes(x.a.n_bones, x.out_stride) + box_lds_bytes<kAosBlock>();
+    int per_cu = 1;
+    if (hipError_t e = aos_blocks_per_cu(&lbs_skin_aos_bounds<EXACT, SHAPES, PL>, lds, &per_cu); e != hipSuccess) return e;
+    uint32_t grid = (uint32_t)kCUs * (uint32_t)per_cu;
+    const uint32_t max_useful = (total + WPB - 1) / WPB;
+    if (grid > max_useful) grid = max_useful;
+    float* slab = bo.slab(bo.user, range_slab_floats(grid, x.a.n_instances));
+    if (!slab) return hipErrorOutOfMemory;
+    hipLaunchKernelGGL((lbs_skin_aos_bounds<EXACT, SHAPES, PL>), dim3(grid), dim3(kAosBlock), lds, s, x, upi, total, slab);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    return launch_bounds_fold(slab, x.a.n_instances, 0, grid, total, upi, bo.out, s);
+}
+
+// With blend shapes the narrow layouts (PL 4 / 5) are skinned by the PL 8 form: at four waves per SIMD the base kernel has 2 of its
+// 128 VGPRs left, too few for the running box (it spilled).  PL only bounds the registers a span may take: the same bits.
+template <bool EXACT, bool SHAPES>
+static hipError_t launch_bounds_aos_one(const LbsExArgs& x, const BoundsOut& bo, hipStream_t s) {
+    switch (lbs_aos_bucket(x.out_stride)) {
+        case 4: if constexpr (SHAPES) return launch_bounds_aos_pl<EXACT, SHAPES, 8>(x, bo, s); else return launch_bounds_aos_pl<EXACT, SHAPES, 4>(x, bo, s);
+        case 5: if constexpr (SHAPES) return launch_bounds_aos_pl<EXACT, SHAPES, 8>(x, bo, s); else return launch_bounds_aos_pl<EXACT, SHAPES, 5>(x, bo, s);
+        case 8: return launch_bounds_aos_pl<EXACT, SHAPES, 8>(x, bo, s);
+        default: return launch_bounds_aos_pl<EXACT, SHAPES, kAosMaxF4PerLane>(x, bo, s);
+    }
+}
+
+hipError_t launch_lbs_aos_bounds(const LbsExArgs& x, const LbsTuning& t, const BoundsOut& bo, hipStream_t s) {
+    if (!lbs_aos_bucket(x.out_stride)) return hipErrorInvalidValue;
+    if (x.a.n_instances == 0) return hipSuccess;
+    if (x.a.n_verts == 0) return launch_bounds_fold(nullptr, x.a.n_instances, 0, 0, 0, 0, bo.out, s);
+    const bool shapes = x.n_shapes > 0;
+    if (t.exact) return shapes ? launch_bounds_aos_one<true, true>(x, bo, s) : launch_bounds_aos_one<true, false>(x, bo, s);
+    return shapes ? launch_bounds_aos_one<false, true>(x, bo, s) : launch_bounds_aos_one<false, false>(x, bo, s);
 }
 
 // ---------------------------------------------------------------------------------------

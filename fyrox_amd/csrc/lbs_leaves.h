@@ -417,4 +417,71 @@ __device__ __forceinline__ void store_vertex_buf(const VtxBuffers& b, uint32_t v
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{o.tx, o.ty, o.tz, tw}), b.out_tan, v * 16u, 0, AUX);
 }
 
+// ---------------------------------------------------------------------------------------
+// Boxes of skinned positions inside the skinning kernels (the *_bounds forms, fyx_lbs_skin_ex_bounds).
+// The reference's fold (AxisAlignedBoundingBox::add_point, fyrox-math/src/aabb.rs:33-104) starts from (+MAX, -MAX) and moves a
+// bound on a strict < / >: a NaN component never enters, infinities do.  Here the six bounds are all kept as MINIMA --
+// (min x, min y, min z, -max x, -max y, -max z) -- so every update is one v_min_f32 (the max half takes its source negated) and
+// every reduction step is the same operation.  minnum(bound, NaN) is the bound (the positions are arithmetic results: quiet
+// NaNs), minnum(+MAX, +inf) is +MAX as +inf < +MAX is false: the same fold, except for the sign of a zero bound, which the
+// reference's own answer leaves to the visiting order.
+// ---------------------------------------------------------------------------------------
+struct BoxAcc {
+    float v[6];
+    __device__ __forceinline__ void reset() {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) v[k] = __FLT_MAX__;
+    }
+    __device__ __forceinline__ void add(float x, float y, float z) {
+        v[0] = __builtin_fminf(v[0], x); v[1] = __builtin_fminf(v[1], y); v[2] = __builtin_fminf(v[2], z);
+        v[3] = __builtin_fminf(v[3], -x); v[4] = __builtin_fminf(v[4], -y); v[5] = __builtin_fminf(v[5], -z);
+    }
+};
+
+// LDS of one workgroup's boxes: component k of wave j's 64 lanes is the run of 64 floats at chunk k * WPB + j, chunks
+// kBoxChunk floats apart (64 + 4: the 16 folding lanes of a b128 read start 16 bytes apart, every bank once).
+constexpr uint32_t kBoxChunk = 68;
+template <int BLOCK>
+constexpr size_t box_lds_bytes() { return (size_t)6 * (BLOCK / 64) * kBoxChunk * sizeof(float); }
+
+template <int BLOCK>
+__device__ __forceinline__ void box_put(const BoxAcc& b, float* lds, uint32_t wave, uint32_t lane) {
+    constexpr uint32_t WPB = BLOCK / 64;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) lds[((uint32_t)k * WPB + wave) * kBoxChunk + lane] = b.v[k];
+}
+
+// One wave folds what box_put left (after a barrier) into the workgroup's partial box out6 = {min xyz, max xyz}: lane k * WPB + j
+// takes wave j's 64 values of component k, then the WPB lanes of a component meet by shuffles.
+template <int BLOCK>
+__device__ __forceinline__ void box_fold(const float* lds, float* out6, uint32_t lane) {
+    constexpr uint32_t WPB = BLOCK / 64;
+    const uint32_t k = lane / WPB;
+    float m = __FLT_MAX__;
+    if (k < 6) {
+        const f32x4* p = reinterpret_cast<const f32x4*>(lds + lane * kBoxChunk);
+        // four b128 reads in flight at a time: the fold runs inside the skinning kernels, whose register budgets have no 64 VGPRs to spare
+#pragma unroll 1
+        for (int i = 0; i < 16; i += 4) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const f32x4 q = p[i + r];
+                m = __builtin_fminf(m, __builtin_fminf(__builtin_fminf(q.x, q.y), __builtin_fminf(q.z, q.w)));
+            }
+        }
+    }
+#pragma unroll
+    for (uint32_t o = 1; o < WPB; o <<= 1) m = __builtin_fminf(m, __shfl_xor(m, (int)o, 64));
+    if (k < 6 && lane % WPB == 0) out6[k] = k < 3 ? m : -m;
+}
+
+// The end of one (workgroup, instance) segment of a kernel that has no barrier there: every thread calls it.  The LDS is rewritten
+// only after the barrier that starts the workgroup's next segment (palette staging), which wave 0 reaches after its fold.
+template <int BLOCK>
+__device__ __forceinline__ void box_segment_end(const BoxAcc& b, float* lds, float* out6, uint32_t wave, uint32_t lane) {
+    box_put<BLOCK>(b, lds, wave, lane);
+    __syncthreads();
+    if (wave == 0) box_fold<BLOCK>(lds, out6, lane);
+}
+
 }  // namespace fyx

@@ -307,6 +307,24 @@ int fyx_lbs_skin_ex(fyx_ctx* ctx, uint64_t mesh_id, const fyx_skin_desc* desc);
  * with or without blend shapes) are skinned by one launch per layout class; plain SoA jobs by one launch per output
  * set; the remaining forms (blend shapes into SoA, custom interleaved layouts) keep one launch each. */
 int fyx_lbs_skin_ex_batch(fyx_ctx* ctx, const uint64_t* mesh_ids, const fyx_skin_desc* descs, uint32_t n_jobs);
+/* fyx_lbs_skin_ex, plus the box of every instance's skinned positions, from the same launch.
+ * d_out_aabb: n_instances x {min xyz, max xyz}, device memory, 4-byte aligned.
+ * What the engine needs of a skinned surface each frame in one pass: the vertices for the renderer and the box
+ * Mesh::accurate_world_bounding_box (fyrox-impl/src/scene/mesh/mod.rs:470-526) computes for culling and picking.
+ *   Vertices: every output is byte-identical to what fyx_lbs_skin_ex writes for the same desc and options, in every form
+ *     (SoA, SoA with blend shapes, a custom interleaved layout, the mesh's own layout).
+ *   Box of instance i: the positions this call computes for instance i (blend-shape offsets included when given), folded as
+ *     AxisAlignedBoundingBox::add_point folds them (fyrox-math/src/aabb.rs:33-104): from (+MAX, -MAX), strict < / > per
+ *     component, so a NaN component never enters a bound (the vertex's other components still do) and infinities do.  The
+ *     sign of a zero bound is unspecified (the reference's depends on the visiting order).  Positions count whether or not
+ *     desc stores them.  An empty mesh gives the default box for every instance.  With lbs.exact = 1 and no blend shapes
+ *     the box is the one fyx_skinned_aabb_device returns for the same palettes.
+ *   Refused as fyx_lbs_skin_ex refuses, and: a null d_out_aabb (FYX_ERR_INVALID_ARG), more than 65535 instances
+ *     (FYX_ERR_UNSUPPORTED).  Nothing is written on a refusal.
+ *   Asynchronous on the stream fyx_lbs_skin_ex would use: the boxes are complete when that stream reaches them (the
+ *     skinning launch writes partial boxes, a small launch behind it on the same stream folds them).  lbs.crowd_lean is
+ *     not honoured here (the default crowd kernel skins: the same bits). */
+int fyx_lbs_skin_ex_bounds(fyx_ctx* ctx, uint64_t mesh_id, const fyx_skin_desc* desc, float* d_out_aabb);
 
 /* Raw-stream form (no registry): all pointers device; d_indices is 4 x u8 per vertex. No bone
  * index validation (caller guarantees indices < n_bones). Asynchronous. */
